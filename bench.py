@@ -1,6 +1,12 @@
 """U-RED training-step benchmark on MI355X (BASELINE.json metric, config 2 by default).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value,
+ms_per_step). --dump-outputs DIR also writes what the last timed step returned (and the model
+state it left) as DIR/<name>.npy. Everything else the benchmark measures (the GEMM roofline and
+per-variant breakdown, the all-slots / 16-part / loader rates, the chamfer, pseudo-label,
+inference and EMD side measurements, the CPU baseline) runs only with --full.
 
 N > 1: under torch.distributed.run (WORLD_SIZE set) each process is one rank; without it,
 bench.py launches the N ranks itself (a torch.distributed.run child process, started before
@@ -501,6 +507,48 @@ def loader_rate(step, eager, cfg, db, dev, steps, world=1, rank=0, warm_epochs=2
                     "copied to the host, host distinct-source tables) + pinned-memory upload inside the timed loop"}
 
 
+DUMP_BUDGET_BYTES = 60 << 20      # --dump-outputs writes at most this much (the limit is 64 MB)
+
+
+def snapshot_outputs(T, step):
+    """What a caller of the timed path holds after its last step, copied to the host: the step's
+    returned dict (the loss terms, the deformed shapes `_out`, the deformation parameters
+    `_params`) as out.<key>, and the state the step left in the models as state.<module>.<key>.
+    float32 stays float32, every other dtype becomes float64."""
+    torch.cuda.synchronize()
+    arrs = {}
+
+    def put(name, v):
+        v = v.detach().cpu()
+        arrs[name] = v.numpy().astype(np.float32 if v.dtype == torch.float32 else np.float64)
+    for k, v in T.items():
+        if torch.is_tensor(v):
+            put("out." + k.lstrip("_"), v)
+    for mod, sd in step.state_dict().items():
+        for k, v in sd.items():
+            put(f"state.{mod}.{k}", v)
+    return arrs
+
+
+def dump_outputs(arrs, out_dir):
+    """DIR/<name>.npy, DUMP_BUDGET_BYTES in all: the arrays share the budget smallest first, and one
+    that exceeds its share is written as a fixed sample of its flattened elements (sorted indices
+    drawn by a generator seeded with the array's name and size, the same in every run)."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    names = sorted(arrs, key=lambda n: (arrs[n].nbytes, n))
+    for i, name in enumerate(names):
+        a = arrs[name]
+        share = left // (len(names) - i)
+        if a.nbytes > share:
+            n = max(1, share // a.itemsize)
+            rng = np.random.default_rng([zlib.crc32(name.encode()), a.size])
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, size=n, replace=False))]
+        left -= a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def _free_port():
     so = socket.socket()
     so.bind(("127.0.0.1", 0))
@@ -567,10 +615,18 @@ def main():
     ap.add_argument("--points", type=int, default=2048)
     ap.add_argument("--parts", type=int, default=4)
     ap.add_argument("--sources", type=int, default=512)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned and the model state it left "
+                         "as DIR/<name>.npy (float32 / float64, at most 64 MB; larger arrays as a fixed sample)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: GEMM roofline and breakdown, the all-slots, "
+                         "16-part and loader rates, the chamfer / pseudo-label / inference / EMD side measurements "
+                         "and the CPU baseline (each can be switched off by its --no-* option)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-breakdown", action="store_true")
     ap.add_argument("--breakdown-steps", type=int, default=3, help="eager steps timed per GEMM launch after the run")
-    ap.add_argument("--shapes-out", default=None, help="write the per-shape GEMM breakdown (JSON) here")
+    ap.add_argument("--shapes-out", default=None,
+                    help="write the per-shape GEMM breakdown (JSON) here (part of the --full breakdown)")
     ap.add_argument("--eager", action="store_true",
                     help="issue the step eagerly (Python + ctypes launches, ~700 per step) instead of replaying it "
                          "as HIP graphs. Graph replay (engine/graph.py, bitwise equal to eager) is the default at "
@@ -599,6 +655,9 @@ def main():
     # path on a one-GPU box (tests); its rates mean nothing
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if not args.full:       # a plain run: the headline only
+        args.no_cpu_baseline = args.no_breakdown = args.no_extras = True
+        args.no_all_slots_rate = args.no_k16_rate = args.no_loader_rate = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
@@ -646,7 +705,7 @@ def main():
         step = eager
 
     b0 = None
-    if use_graph:
+    if use_graph and args.full:
         # the dominant GEMM variant's launches / FLOPs / bytes per step (for the roofline) from one
         # eager step with an event pair per GEMM launch, before the graphs are captured; one plain
         # eager step first, so that no kernel's first launch (code-object load) is among them
@@ -659,7 +718,7 @@ def main():
     # one more untimed step with an event pair per GEMM launch picks the dominant kernel
     # variant, whose launches are then timed inside the timed region itself (eager mode)
     dom = None
-    if not use_graph:
+    if not use_graph and args.full:
         with GemmTimer() as gt0:
             eager.step(batches[args.warmup % 4])
         b0 = gt0.summary()
@@ -685,6 +744,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
     loss_val = float(T["all_loss"].item())
+    if args.dump_outputs and rank == 0:      # before any --full side run trains the models further
+        dump_outputs(snapshot_outputs(T, step), args.dump_outputs)
 
     def timed_rate(steps, bs=None):
         """A side workload under the headline's protocol: the same step mode (HIP-graph replay
@@ -873,7 +934,7 @@ def main():
     out = {"metric": "train iters/sec chair bs=16 2048-pt @1/2/4/8 GPU; Chamfer Gpair-dist/s",
            "value": round(iters_per_s * world, 4), "unit": "iters/s", "n_gpus": world, "steps": args.steps,
            "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak",
-           "step_mode": "hip_graph" if use_graph else "eager",
+           "step_mode": "hip_graph" if use_graph else "eager", "full": bool(args.full),
            "vs_baseline": None, "dtype": "f32", "data": "synthetic (SURVEY §8d generator; random-init weights)",
            "config": {"workload": "config 2: chair, full U-RED train step, bs=16/GPU, 2048 pts, 16x1024 source pts, "
                                   "C=512, S=128, 4 parts/target", "global_batch": args.batch * world,

@@ -29,3 +29,31 @@ def test_bench_two_ranks_gloo(dev):
     assert d["step_mode"] == "hip_graph"
     assert d["value"] > 0 and d["config"]["global_batch"] == 8
     print(lines[0][:300])
+
+
+@pytest.mark.timeout(200)
+def test_bench_plain_run_dumps_outputs(dev, tmp_path):
+    """A plain run (no --full) times exactly --steps steps, prints the headline line without the
+    side measurements, and --dump-outputs leaves the last step's outputs and the model state."""
+    import numpy as np
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--batch", "4", "--points", "512", "--dump-outputs", str(out)]
+    p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=180)
+    assert p.returncode == 0, p.stderr[-5000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-3000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["n_gpus"] == 1 and d["full"] is False
+    assert d["unit"] == "iters/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["ms_per_step"] > 0 and abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 1e-3
+    assert d["roofline"] is None and d["cpu_baseline"] is None
+    for k in ("gemm_variants", "all_slots_iters_s", "k16_iters_s", "loader", "chamfer", "inference", "emd"):
+        assert k not in d, k
+    files = {f.name: np.load(f) for f in out.iterdir()}
+    assert "out.all_loss.npy" in files and "out.out.npy" in files
+    assert any(n.startswith("state.src_encoder_all.") for n in files)
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert float(files["out.all_loss.npy"]) == pytest.approx(d["loss"], rel=1e-6)
+    assert files["out.out.npy"].shape[0] == 4 and np.isfinite(files["out.out.npy"]).all()

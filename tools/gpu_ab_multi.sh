@@ -4,7 +4,7 @@
 set -o pipefail
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
-B="--no-cpu-baseline --no-all-slots-rate --no-k16-rate --no-extras --steps 30"
+B="--full --no-cpu-baseline --no-all-slots-rate --no-k16-rate --no-extras --steps 30"
 N=${REPS:-3}
 for rep in $(seq $N); do
   for v in "$@"; do

@@ -3,7 +3,7 @@
 set -o pipefail
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
-B="--no-cpu-baseline --no-all-slots-rate --no-k16-rate --no-extras --steps 30"
+B="--full --no-cpu-baseline --no-all-slots-rate --no-k16-rate --no-extras --steps 30"
 for rep in $(seq ${REPS:-3}); do
   for L in "$@"; do
     r=$(URED_LIB=$L timeout -k 10 200 python3 bench.py $B 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.load(sys.stdin); print(d['value'], 'gemm_ms', d['gemm_all']['ms_per_step'])") || exit 1
