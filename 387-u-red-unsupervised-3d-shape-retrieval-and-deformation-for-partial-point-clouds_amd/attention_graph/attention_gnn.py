@@ -10,8 +10,6 @@ kernel each way (ured_hip.attn), out_proj as a node GEMM, and the FeedForwardNet
 BatchNorm kernel, the concatenation [x, message] read in place. `forward` keeps the
 reference's channel-first signature for drop-in callers.
 """
-import os
-
 import torch
 import torch.nn as nn
 
@@ -21,9 +19,6 @@ from ured_hip.node import node_ffn, node_linear, node_proj
 from . import get_attention_mechanism
 from .attention import softmax_attention
 from .attention_utils import FeedForwardNet_norm, conv1x1
-
-_ATTN_PAIR = os.environ.get("URED_ATTN_PAIR", "1") == "1"     # A/B knob (tools/gpu_py_ab.sh)
-_NODE_ALIAS = os.environ.get("URED_NODE_ALIAS", "1") == "1"   # A/B knob (tools/gpu_py_ab.sh)
 
 
 class MultiheadAttention(nn.Module):
@@ -107,11 +102,8 @@ class ResidualAttentionMessagePropagation(nn.Module):
             first = xq - message if self.use_offset else xq
             return xq + self.fc.forward_nodes(torch.cat([first, message], dim=-1)), xkv
         B, n, C = xq.shape
-        if _NODE_ALIAS:
-            message, x2, xkv_a = self.mha.forward_nodes(xq, xkv, alias=True)
-            xkv_a = None if xkv_a is None else xkv_a.view(xkv.shape)
-        else:
-            message, x2, xkv_a = self.mha.forward_nodes(xq, xkv), xq.reshape(B * n, C), xkv
+        message, x2, xkv_a = self.mha.forward_nodes(xq, xkv, alias=True)
+        xkv_a = None if xkv_a is None else xkv_a.view(xkv.shape)
         m2 = message.reshape(B * n, C)
         first, R = (x2 - m2, x2) if self.use_offset else (x2, None)
         return node_ffn(self.fc, first, m2, R, (0, B * n)).view(B, n, C), xkv_a
@@ -135,17 +127,10 @@ class ResidualAttentionMessagePropagation(nn.Module):
         X = torch.cat([x0.reshape(R0, C), x1.reshape(R1, C)])
         q_, k_, v_ = mha.in_proj_q, mha.in_proj_k, mha.in_proj_v
         # X's second consumer (the FFN) reads the projection's alias of it (NodeProjFn)
-        qkv = node_proj((X,), [(mha._w(q_), mha._w(k_), mha._w(v_))], [(q_.bias, k_.bias, v_.bias)],
-                        aliases=(_NODE_ALIAS,))
-        if _NODE_ALIAS:
-            qkv, X = qkv
-        if _ATTN_PAIR:
-            # both sets' attention in one launch each way, reading / writing row blocks of qkv / o
-            o = self_attention_pair(qkv, B, n0, n1, mha.num_heads)
-        else:
-            q0, q1 = qkv.split([R0, R1])
-            o = torch.cat([self_attention(q0.view(B, n0, -1), mha.num_heads).reshape(R0, C),
-                           self_attention(q1.view(B, n1, -1), mha.num_heads).reshape(R1, C)])
+        qkv, X = node_proj((X,), [(mha._w(q_), mha._w(k_), mha._w(v_))], [(q_.bias, k_.bias, v_.bias)],
+                           aliases=(True,))
+        # both sets' attention in one launch each way, reading / writing row blocks of qkv / o
+        o = self_attention_pair(qkv, B, n0, n1, mha.num_heads)
         message = node_linear(o, mha._w(mha.out_proj), mha.out_proj.bias)
         first, R = (X - message, X) if self.use_offset else (X, None)
         out0, out1 = node_ffn(self.fc, first, message, R, (0, R0, R0 + R1)).split([R0, R1])

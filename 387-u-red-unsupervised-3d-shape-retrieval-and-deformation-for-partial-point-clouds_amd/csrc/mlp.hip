@@ -36,10 +36,6 @@ constexpr int BM = 128, BN = 128, BK = 32, NT = 256;
 typedef float f16v __attribute__((ext_vector_type(16)));
 typedef float f2v __attribute__((ext_vector_type(2)));
 
-struct Gemm {
-    UredGemmDesc d;
-};
-
 __device__ __forceinline__ float pro_apply(int pro, float x, float s, float t) {
     if (pro == URED_PRO_ENC) return fmaxf(__builtin_fmaf(x, s, t), 0.f);
     if (pro == URED_PRO_RES) return __builtin_fmaf(fmaxf(x, 0.f), s, t);
@@ -201,17 +197,6 @@ __device__ __forceinline__ void store_kmajor(const RowTile& r, float* S) {
 }
 
 template <bool KM> struct Pad { static constexpr int v = KM ? BM + 4 : BM + 1; };
-
-// streaming kernels for the K <= 4 edge layers (A/B switches, one per direction)
-#ifndef URED_FWD_SMALL
-#define URED_FWD_SMALL 1
-#endif
-#ifndef URED_DGRAD_SMALL
-#define URED_DGRAD_SMALL 1
-#endif
-#ifndef URED_BNBWD_YALL
-#define URED_BNBWD_YALL 1
-#endif
 
 // BN partials (EPI_FWD stat_ws {mean, M2}, EPI_BNBWD bwd_ws {sum g, sum g*xhat}): layout
 // [2][N][nblk], nblk = ceil(M/128) — one column's block partials are contiguous, so the
@@ -617,23 +602,19 @@ __device__ __forceinline__ void epilogue(const UredGemmDesc& d, f16v (&acc)[2][2
                 else bnbwd_full<URED_ACT_ENC, false, TN>(d, acc, m0, n0, s1, s2, pre);
             }
         } else {
-        // Yp one column half (32 values) at a time: the j = 0 half and the per-column
-        // parameters are issued before pre() (the persistent kernel's next-tile DMA), the j = 1
-        // half after the j = 0 half is processed (registers: acc 64 + one half 32)
-        // URED_BNBWD_YALL: both halves (64 values) are issued at once instead — after the K-loop
-        // the fragment registers are dead, so the whole tile fits without raising the kernel's
-        // VGPR peak, and the epilogue then waits for one HBM round trip instead of two (gfx9
-        // vmcnt is in order: the second half's loads otherwise queue behind the first half's stores)
-        f16v yh[URED_BNBWD_YALL ? 2 : 1][2];
+        // Yp is loaded whole (both column halves, 64 values) before pre(), the persistent kernel's
+        // next-tile DMA: after the K-loop the fragment registers are dead, so the tile fits under
+        // the kernel's VGPR peak, and the epilogue waits for one HBM round trip instead of two
+        // (gfx9 vmcnt is in order: a second half's loads would queue behind the first half's stores)
+        f16v yh[2][2];
         InTile<BUFST> Yr(d.Yp, d.ldy, d.M, d.N);
         auto load_y = [&](int j) {
             const int col = n0 + wn * (32 * TN) + j * 32 + (lane & 31);
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) yh[URED_BNBWD_YALL ? j : 0][i][r] = Yr.get(row_of(i, r), col);
+                for (int r = 0; r < 16; ++r) yh[j][i][r] = Yr.get(row_of(i, r), col);
         };
-        if (!URED_BNBWD_YALL) load_y(0);
         // max-pool backward: the pooled gradient lands on the winning row of each (group, column)
         const bool pool_blk = d.pool_idx && (d.pool_group_rows % BM == 0);
         const int pg = pool_blk ? m0 / d.pool_group_rows : 0;
@@ -648,7 +629,7 @@ __device__ __forceinline__ void epilogue(const UredGemmDesc& d, f16v (&acc)[2][2
             pidx_[j] = -1; pgr_[j] = 0.f;
             if (pool_blk && cv) { pidx_[j] = d.pool_idx[(size_t)pg * d.N + col]; pgr_[j] = d.pool_grad[(size_t)pg * d.N + col]; }
         }
-        if (URED_BNBWD_YALL) { load_y(0); load_y(1); }   // behind the (L2-resident) per-column parameters
+        load_y(0); load_y(1);   // behind the (L2-resident) per-column parameters
         pre();
         OutTile<BUFST> Gw(d.C, d.ldc, d.M, d.N);
         // per-element global reads (a residual gradient, or pooled gradients of groups that do
@@ -658,7 +639,6 @@ __device__ __forceinline__ void epilogue(const UredGemmDesc& d, f16v (&acc)[2][2
         const float ylo = d.bwd_res == URED_ACT_RES ? 0.f : -__builtin_inff();
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-            if (!URED_BNBWD_YALL && j == 1) load_y(1);
             const int col = n0 + wn * (32 * TN) + j * 32 + (lane & 31);
             const bool cv = col < d.N;
             const float sc = sc_[j], sh = sh_[j], mu = mu_[j], is = is_[j];
@@ -678,7 +658,7 @@ __device__ __forceinline__ void epilogue(const UredGemmDesc& d, f16v (&acc)[2][2
                         const bool ok = cv && row < d.M;
                         const float a = acc[i][j][r];
                         const float dh = (row == pidx) ? a + pgr : a;
-                        const float y = yh[URED_BNBWD_YALL ? j : 0][i][r];
+                        const float y = yh[j][i][r];
                         const float xh = (fmaxf(y, ylo) - mu) * is;
                         const float g = (__builtin_fmaf(y, sck, shk) > 0.f) ? dh : 0.f;
                         Gw.put(ok, row, col, g);
@@ -700,7 +680,7 @@ __device__ __forceinline__ void epilogue(const UredGemmDesc& d, f16v (&acc)[2][2
                         if (d.pool_idx[ge] == row) dh += d.pool_grad[ge];
                     }
                     if (d.gadd && ok) dh += d.gadd[(size_t)row * d.ldg + col];
-                    const float y = yh[URED_BNBWD_YALL ? j : 0][i][r];
+                    const float y = yh[j][i][r];
                     float g, xh;
                     if (d.bwd_res == URED_ACT_RES) {
                         g = dh;
@@ -848,20 +828,7 @@ typedef __attribute__((address_space(3))) void lds_void_t;
 // k >= K row of a k-major operand: the hardware returns zeros for them.
 constexpr unsigned BUF_OOB = 0x80000000u;
 constexpr int PRO_LDS = 1024;            // max prologue channels staged in LDS by gemm2
-// 64-wide block tiles for the narrow layers (gemm2_kernel TM / TN); 0 = 128 x 128 everywhere
-#ifndef URED_GEMM_NARROW
-#define URED_GEMM_NARROW 1
-#endif
-// Where a K-step issues the next step's LDS-DMA: 0 = before its fragment reads, 1 = in two
-// halves between MFMA groups (rounds 3-4), 2 = right behind its fragment reads, ahead of every
-// MFMA (round 5 default: DESIGN.md, "The multi-process fault"; 0.9 % of the step vs 1)
-#ifndef URED_DMA_SPREAD
-#define URED_DMA_SPREAD 2
-#endif
 constexpr int BUF_DWORD3 = 0x00020000;   // raw buffer, gfx9 family (gfx950)
-#ifndef URED_EXP_DGRAD_PRO
-#define URED_EXP_DGRAD_PRO 0
-#endif
 
 __host__ __device__ inline bool buf_ok(const UredGemmDesc& d) {
     // a concatenated second A source must start on a K-step boundary (one descriptor per step)
@@ -1045,10 +1012,8 @@ __global__ __launch_bounds__(NT, 2) void gemm2_kernel(const UredGemmDesc d) {
         const float* As = smem + stage * 2 * TILE;
         const float* Bs = As + TILE;
         const bool tail = k0 + BK > kend;
-        // next step's DMA goes into the other stage (its last readers passed the barrier
-        // above); URED_DMA_SPREAD picks the issue point (see its definition)
+        // next step's DMA goes into the other stage (its last readers passed the barrier above)
         const bool next = k0 + BK < kend && !both;
-        if (URED_DMA_SPREAD == 0 && next) { issue_a(stage ^ 1, k0 + BK); issue_b(stage ^ 1, k0 + BK); }
 
         // the prologue's scale/shift first: LDS reads complete in issue order, so the
         // prologue (and the MFMAs behind it) can start on the first A fragments
@@ -1100,9 +1065,11 @@ __global__ __launch_bounds__(NT, 2) void gemm2_kernel(const UredGemmDesc d) {
             }
         }
 
-        // URED_DMA_SPREAD == 2: the next step's DMA right behind this step's fragment reads, in
-        // front of every MFMA (the fence keeps the scheduler from sinking it among them)
-        if (URED_DMA_SPREAD == 2 && next) {
+        // the next step's DMA right behind this step's fragment reads, ahead of every MFMA (the
+        // fence keeps the scheduler from sinking it among them). Issued in halves between MFMA
+        // groups it was 0.9 % of the step faster, but that placement corrupted another process's
+        // results in round 4's multi-process probe ("The multi-process fault")
+        if (next) {
             issue_a(stage ^ 1, k0 + BK);
             issue_b(stage ^ 1, k0 + BK);
             __builtin_amdgcn_sched_barrier(0);
@@ -1135,9 +1102,6 @@ __global__ __launch_bounds__(NT, 2) void gemm2_kernel(const UredGemmDesc d) {
         // variants +1-2 % isolated (tools/ab_libs_step.sh, same box, two rounds); the BN-backward
         // dgrad went -1..+1 %, so it keeps the plain schedule
         constexpr bool PRIO = EPI != URED_EPI_BNBWD;
-        // URED_DMA_SPREAD == 1: MFMA group (of 16) behind which the next step's A / B halves are
-        // issued: 6 / 11 with a k-major B, 1 / 5 with a row-major B (profiles/r4zh_*)
-        constexpr int DMA_JA = B_KM ? 6 : 1, DMA_JB = B_KM ? 11 : 5;
         if (PRIO) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
@@ -1146,8 +1110,6 @@ __global__ __launch_bounds__(NT, 2) void gemm2_kernel(const UredGemmDesc d) {
 #pragma unroll
                 for (int tn = 0; tn < TN; ++tn)
                     acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[tm][j], b[tn][j], acc[tm][tn], 0, 0, 0);
-            if (URED_DMA_SPREAD == 1 && next && j == DMA_JA) issue_a(stage ^ 1, k0 + BK);
-            if (URED_DMA_SPREAD == 1 && next && j == DMA_JB) issue_b(stage ^ 1, k0 + BK);
         }
         if (PRIO) __builtin_amdgcn_s_setprio(0);
         stage ^= 1;
@@ -1755,7 +1717,7 @@ __global__ __launch_bounds__(SMALL_NT) void fwd_small_stats_kernel(const UredGem
 
 bool fwd_small_ok(const UredGemmDesc& d) {
     // the kernel reads A and B raw: no prologue on either operand
-    return URED_FWD_SMALL && d.epi == URED_EPI_FWD && !d.a_kmajor && !d.b_kmajor && d.pro_a == URED_PRO_NONE &&
+    return d.epi == URED_EPI_FWD && !d.a_kmajor && !d.b_kmajor && d.pro_a == URED_PRO_NONE &&
            d.pro_b == URED_PRO_NONE && d.K >= 1 && d.K <= 4 && d.N >= 1 && d.N <= 256 && !d.pool_ws && !d.rowbias &&
            d.k1 == d.K;
 }
@@ -1772,7 +1734,7 @@ void launch_fwd_small(const UredGemmDesc& d, hipStream_t st) {
 
 bool dgrad_small_ok(const UredGemmDesc& d) {
     // the kernel reads A and B raw: no prologue on either operand
-    return URED_DGRAD_SMALL && d.epi == URED_EPI_BNBWD && !d.a_kmajor && d.b_kmajor && d.pro_a == URED_PRO_NONE &&
+    return d.epi == URED_EPI_BNBWD && !d.a_kmajor && d.b_kmajor && d.pro_a == URED_PRO_NONE &&
            d.pro_b == URED_PRO_NONE && d.K >= 1 && d.K <= 4 && d.N >= 1 && d.N <= 256 && !d.pool_idx && d.k1 == d.K;
 }
 
@@ -1795,8 +1757,8 @@ void launch(const UredGemmDesc& d, hipStream_t st) {
     if (vec_ok(d) && v2_ok(d) && buf_ok(d)) {
         // narrow tiles for outputs of <= 64 columns (and, split-K / store only, <= 64 rows)
         constexpr bool NARROW_M = EPI == URED_EPI_SPLITK || EPI == URED_EPI_STORE;
-        const bool tn1 = URED_GEMM_NARROW && d.N <= 64;
-        const bool tm1 = URED_GEMM_NARROW && NARROW_M && d.M <= 64;
+        const bool tn1 = d.N <= 64;
+        const bool tm1 = NARROW_M && d.M <= 64;
         grid.x = ((d.M + (tm1 ? 63 : 127)) / (tm1 ? 64 : 128)) * ((d.N + (tn1 ? 63 : 127)) / (tn1 ? 64 : 128));
         if (tm1 && tn1) hipLaunchKernelGGL((gemm2_kernel<A_KM, B_KM, PA, PB, EPI, NARROW_M ? 1 : 2, 1>), grid, dim3(NT), 0, st, d);
         else if (tm1) hipLaunchKernelGGL((gemm2_kernel<A_KM, B_KM, PA, PB, EPI, NARROW_M ? 1 : 2, 2>), grid, dim3(NT), 0, st, d);
@@ -1826,11 +1788,6 @@ int dispatch(const UredGemmDesc& d, hipStream_t st) {
         // dgrad
         URED_CASE(0, 1, URED_PRO_NONE, URED_PRO_NONE, URED_EPI_BNBWD)
         URED_CASE(0, 1, URED_PRO_NONE, URED_PRO_NONE, URED_EPI_STORE)
-#if URED_EXP_DGRAD_PRO
-        // measurement build only (tools/gemm_bench.py dgrad_bnbwd_pro): the BN-backward dgrad with the
-        // forward's one-input A prologue, the lower bound of folding the BN-backward apply into it
-        URED_CASE(0, 1, URED_PRO_ENC, URED_PRO_NONE, URED_EPI_BNBWD)
-#endif
         // few output tiles, long K (per-group codes, fc layers): split-K partials
         URED_CASE(0, 0, URED_PRO_NONE, URED_PRO_NONE, URED_EPI_SPLITK)
         URED_CASE(0, 1, URED_PRO_NONE, URED_PRO_NONE, URED_EPI_SPLITK)

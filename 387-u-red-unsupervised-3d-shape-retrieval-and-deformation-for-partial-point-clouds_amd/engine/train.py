@@ -54,8 +54,6 @@ from train_utils.optimizer_dm import define_optimizer_dm_re_recon  # noqa: E402
 from ured_hip.kernels import RowWeights  # noqa: E402
 from ured_hip.ops import PartBounds, UniqueRows, build_parts, part_aabb, part_rows, upload  # noqa: E402
 
-_SHAPE_SRC = os.environ.get("URED_SHAPE_SRC", "1") == "1"     # A/B knob (tools/gpu_py_ab.sh)
-
 MODULE_NAMES = ("target_encoder_full", "param_decoder_full", "recon_decoder_full", "re_residual_net_full",
                 "src_encoder_all", "recon_decoder_src", "embedding_layer")
 CLIPPED = ("target_encoder_full", "param_decoder_full", "re_residual_net_full", "recon_decoder_full",
@@ -238,7 +236,7 @@ class TrainStep:
         uq = batch.get("src_unique") if cfg.get("unique_sources", True) else None
         # the unique-source path embeds the distinct parts' semantics itself (_source_branch); the
         # source matrices are read in place by get_shape_src
-        mats, _, src_sem_idx = get_source_info(src_labels, self.db, want=(not _SHAPE_SRC, False, uq is None))
+        _, _, src_sem_idx = get_source_info(src_labels, self.db, want=(False, False, uq is None))
         emb = M["embedding_layer"]
         with torch.no_grad():          # the embedding is not trained (optimizer_dm.py:83)
             src_sem_f = emb(src_sem_idx) if uq is None else None
@@ -254,8 +252,7 @@ class TrainStep:
                                                                                  batch["labels"], x, alias=True)
         codes = codes.view(B, P, -1)
         params_full = M["param_decoder_full"](tcode, codes, None)
-        out = (get_shape_src(self.db, src_labels, params_full, param_def, cfg["alpha"]) if _SHAPE_SRC else
-               get_shape(mats, params_full, param_def, cfg["alpha"])).reshape(B, -1, 3)
+        out = get_shape_src(self.db, src_labels, params_full, param_def, cfg["alpha"]).reshape(B, -1, 3)
         recon_full_p = M["recon_decoder_full"].forward_split(pp_alias.view(B * N, -1), tcode,
                                                              group_rows=N).view(B, N, 3)
         re_res = M["re_residual_net_full"].forward_split(re_in.pp_sorted, re_in.part_mean, gidx=re_in.gid,

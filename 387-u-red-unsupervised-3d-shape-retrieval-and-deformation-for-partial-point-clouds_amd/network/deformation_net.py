@@ -11,7 +11,7 @@ import torch.nn as nn
 
 from attention_graph.attention_gnn import GraphAttentionNet
 from attention_graph.attention_utils import FeedForwardNet_norm
-from ured_hip.mlp import ResidualNetFn
+from ured_hip.mlp import ResidualNetFn, ResidualSpec
 from ured_hip.node import param_decoder as node_param_decoder
 
 
@@ -76,7 +76,7 @@ class re_residual_net(nn.Module):
         rw: optional ured_hip.kernels.RowWeights (unique-row batch, see ResidualNetFn).
         """
         params, bns = self._params()
-        spec = (code_first, gidx, off, group_rows, self.training, bns, rw)
+        spec = ResidualSpec(code_first, gidx, off, group_rows, self.training, bns, rw)
         return ResidualNetFn.apply(spec, pp, code, *params)
 
     def forward(self, concat_feature):

@@ -3,7 +3,7 @@
   _lib     ctypes loader of the C-ABI (include/ured_hip.h); raises if missing
   nn       nearest-neighbour / chamfer autograd ops (dense + ragged segments)
   kernels  typed wrappers of the fused per-point MLP entry points
-  mlp      PointEncoderFn / ResidualNetFn autograd chains
+  mlp      PointEncoderFn / ResidualNetFn / PointChainFn autograd chains
   attn     graph-node multi-head attention (DeformNet's GraphAttentionNet core)
   optim    FlatAdam: per-module gradient clipping + Adam over flat buffers
   node     DeformNet graph-node GEMM / BatchNorm launches

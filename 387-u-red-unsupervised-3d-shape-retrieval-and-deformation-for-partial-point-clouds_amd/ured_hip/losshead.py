@@ -21,7 +21,6 @@ Terms vector layout (slots): 0 cd_full, 1 cd_part, 2 ref_cd_full, 3 ref_cd_part,
 """
 import ctypes
 import math
-import os
 
 import torch
 from torch.autograd import Function
@@ -39,7 +38,6 @@ class PointLossDesc(ctypes.Structure):
 
 
 ASSEMBLE_MAX = 16
-USE_PART_BOUNDS = os.environ.get("URED_PART_BOUNDS", "1") != "0"   # A/B knob: 0 = slot bounds
 _lib.register({
     "ured_cd_pair_prep": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "ured_cd_pair_reduce": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P],
@@ -113,7 +111,7 @@ class HeadInputs:
         (S deformed points, N target points) or, with the batch's host-side PartBounds, the most
         parts x points per part and the largest part (every segment lies within them)."""
         b = self.bounds
-        if b is None or not USE_PART_BOUNDS:
+        if b is None:
             return S, N
         return min(S, b.k * self.np), min(N, b.count)
 

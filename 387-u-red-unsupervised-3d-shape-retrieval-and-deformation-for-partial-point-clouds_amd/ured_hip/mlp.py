@@ -10,9 +10,17 @@ ResidualNetFn  : re_residual_net.forward (network/deformation_net.py:96-107) wit
                  input is cat(per-point features, per-group code): the group half
                  is folded into a per-group row bias (W_code @ code), so it is
                  never broadcast to every point.
-Both run forward and backward entirely on HIP kernels; only the tiny
-per-call index bookkeeping is Python.
+PointChainFn   : the PointNet conv stacks (STN3d / STNkd / PointNetEncoder,
+                 network/pointnet/pointnet_utils.py): L x Conv1d+BatchNorm1d(+ReLU),
+                 then a max-pool over each cloud and/or the last activation.
+All three run forward and backward entirely on HIP kernels; only the tiny
+per-call index bookkeeping is Python. A chain is a loop over _layer_fwd /
+_layer_bwd (one Conv+BN layer each way); a Function adds only its own special
+layer (fuse_sem + pooling, the row-bias first layer, the K = 0 last layer) and
+its head.
 """
+from typing import Any, NamedTuple
+
 import torch
 from torch.autograd import Function
 
@@ -55,13 +63,66 @@ def _nbt(bnm):
     return t
 
 
-def _bn_state(spec, i, Yws, M, N, gamma, beta):
-    bnm = spec.bn_modules[i]
-    if spec.training:
+def _bn_state(bnm, training, rw, sws, M, N, gamma, beta, eps):
+    """BN state of a layer from its GEMM's statistics partials (training: batch statistics, the
+    module's running stats and num_batches_tracked updated in place) or its running stats (eval)."""
+    if training:
         mom = bnm.momentum if bnm.momentum is not None else 0.0
-        return K.bn_fwd_finalize(Yws, M, N, gamma, beta, spec.eps, mom, bnm.running_mean, bnm.running_var, rw=spec.rw,
+        return K.bn_fwd_finalize(sws, M, N, gamma, beta, eps, mom, bnm.running_mean, bnm.running_var, rw=rw,
                                  num_batches_tracked=_nbt(bnm))
-    return K.bn_eval_state(gamma, beta, bnm.running_mean, bnm.running_var, spec.eps)
+    return K.bn_eval_state(gamma, beta, bnm.running_mean, bnm.running_var, eps)
+
+
+def _layer_fwd(i, params, h, Kdim, pro, st, bnm, training, rw, *, eps=BN_EPS, stat_relu=False, special=None):
+    """Forward of Conv1d(k=1) + BatchNorm1d layer i of a chain (params W,b,gamma,beta at 4*i):
+    Y = pro(h)[:, :Kdim] @ W^T + b in one GEMM, the previous layer's BN (st, applied in order
+    `pro`) as its prologue and this layer's batch-statistics partials as its epilogue, then this
+    layer's BN state. special(N) -> further GEMM arguments of a chain's one special layer; it runs
+    after Y and the statistics workspace are allocated. Returns (Y, state)."""
+    W = params[4 * i].reshape(params[4 * i].shape[0], -1)
+    M, N = h.shape[0], W.shape[0]
+    Y = torch.empty(M, N, device=h.device)
+    sws = torch.empty(K.nblocks(M), 2, N, device=h.device)
+    kw = {} if special is None else special(N)
+    K.gemm(M, N, Kdim, h, h.shape[1], W, W.shape[1], Y, N, pro_a=pro,
+           pro_s=None if st is None else st.scale, pro_t=None if st is None else st.shift,
+           bias=params[4 * i + 1], epi=K.EPI_FWD, stat_ws=sws, stat_relu=stat_relu, **kw)
+    return Y, _bn_state(bnm, training, rw, sws, M, N, params[4 * i + 2], params[4 * i + 3], eps)
+
+
+def _layer_bwd(i, params, grads, bias, x, Ys, states, dY, Wn, act, pro, rw, *, Kdim=None, out_off=0, special=None,
+               **kw):
+    """Backward of layer i of a chain, from dY = the gradient at the output of the layer above
+    and Wn = that layer's weight: the fused dgrad dH_i = dY @ Wn[:, :N] with the activation mask
+    (act: K.ACT_*) and the BN-backward partials of layer i in its epilogue (Kdim = 0: no layer
+    above, the gradient enters through the epilogue's kw alone), the BN-backward finalize and
+    apply, the weight gradient against the layer's input (x, or the layer below's Y under its BN
+    as prologue, order `pro`; out_off: first weight column), then special(dYi, cs, dW) for the
+    weight columns a chain's special layer adds. The bias column sums are queued on `bias`, the
+    four gradients go to grads[4*i..]. Returns (dY_i, W_i) for the layer below."""
+    Y, st = Ys[i], states[i]
+    M, N = Y.shape
+    G_ = torch.empty(M, N, device=Y.device)
+    bws = torch.empty(K.nblocks(M), 2, N, device=Y.device)
+    K.gemm(M, N, dY.shape[1] if Kdim is None else Kdim, dY, dY.shape[1], Wn, Wn.shape[1], G_, N, b_kmajor=True,
+           epi=K.EPI_BNBWD, Yp=Y, ldy=N, bn=st, bwd_res=act, bwd_ws=bws, **kw)
+    gamma = params[4 * i + 2]
+    dgamma, dbeta = grad_buffer(gamma), grad_buffer(params[4 * i + 3])
+    coefs = K.bn_bwd_finalize(bws, M, N, gamma, st.invstd, dgamma, dbeta, rw=rw)
+    dYi, cs = K.bn_bwd_apply(G_, Y, act == K.ACT_RES, st.mean, coefs, rw=rw)
+    W = params[4 * i].reshape(params[4 * i].shape[0], -1)
+    dW, db = grad_buffer(params[4 * i]).view(W.shape), grad_buffer(params[4 * i + 1])
+    X, stp = (x, None) if i == 0 else (Ys[i - 1], states[i - 1])
+    kin = X.shape[1]
+    K.wgrad(dYi, N, X, kin, N, kin, M, dW, W.shape[1], out_off=out_off, pro=K.PRO_NONE if stp is None else pro,
+            pro_s=None if stp is None else stp.scale, pro_t=None if stp is None else stp.shift)
+    if special is not None:
+        special(dYi, cs, dW)
+    bias.add(cs, db)
+    grads[4 * i] = dW.view(params[4 * i].shape)
+    grads[4 * i + 1] = db
+    grads[4 * i + 2], grads[4 * i + 3] = dgamma, dbeta
+    return dYi, W
 
 
 class PointEncoderFn(Function):
@@ -75,48 +136,42 @@ class PointEncoderFn(Function):
         GR = spec.group_rows
         G = M // GR
         dev = x.device
-        Ws = [params[4 * i].reshape(params[4 * i].shape[0], -1) for i in range(7)]
-        bs = [params[4 * i + 1] for i in range(7)]
-        gs = [params[4 * i + 2] for i in range(7)]
-        bes = [params[4 * i + 3] for i in range(7)]
         W8, b8, fcW, fcb = params[28].reshape(params[28].shape[0], -1), params[29], params[30], params[31]
+        S = sem.shape[1]
         Ys, states = [], []
-        h, kin, pro, st = x, 3, K.PRO_NONE, None
+        h, pro, st = x, K.PRO_NONE, None
         pool_ws = None
+
+        def fuse_sem(N):   # (1024 + S) -> 1024, then max-pool over each group
+            nonlocal pool_ws
+            kin = Ys[4].shape[1]
+            kw = dict(group_rows=GR)
+            if GR % K.BM == 0:   # pooling partials fused into the GEMM epilogue
+                pool_ws = torch.empty(K.nblocks(M), 4, N, device=dev)
+                kw.update(pool_ws=pool_ws)
+            if spec.mode == "src":   # per-group semantics: a row bias
+                W6 = params[20].reshape(N, -1)
+                rb = torch.empty(G, N, device=dev)
+                K.gemm(G, N, S, sem, S, W6, W6.shape[1], rb, N, B_off=kin)
+                kw.update(rowbias=rb, ldr=N)
+            else:                    # per-point semantics: further K columns
+                kw.update(A2=sem, lda2=S, k1=kin)
+            return kw
+
         for i in range(7):
-            W = Ws[i]
-            N = W.shape[0]
-            Y = torch.empty(M, N, device=dev)
-            sws = torch.empty(K.nblocks(M), 2, N, device=dev)
-            kw = {}
-            if i == 5:   # fuse_sem: (1024 + S) -> 1024, then max-pool over each group
-                if GR % K.BM == 0:   # pooling partials fused into the GEMM epilogue
-                    pool_ws = torch.empty(K.nblocks(M), 4, N, device=dev)
-                    kw.update(pool_ws=pool_ws)
-                kw.update(group_rows=GR)
-                S = sem.shape[1]
-                if spec.mode == "src":
-                    rb = torch.empty(G, N, device=dev)
-                    K.gemm(G, N, S, sem, S, W, W.shape[1], rb, N, B_off=kin)
-                    kw.update(rowbias=rb, ldr=N)
-                    Kdim = kin
-                else:
-                    kw.update(A2=sem, lda2=S, k1=kin)
-                    Kdim = kin + S
-            else:
-                Kdim = kin
-            K.gemm(M, N, Kdim, h, h.shape[1], W, W.shape[1], Y, N, pro_a=pro,
-                   pro_s=None if st is None else st.scale, pro_t=None if st is None else st.shift,
-                   bias=bs[i], epi=K.EPI_FWD, stat_ws=sws, **kw)
-            st = _bn_state(spec, i, sws, M, N, gs[i], bes[i])
-            Ys.append(Y)
+            kin = h.shape[1]
+            Kdim = kin + S if i == 5 and spec.mode == "tgt" else kin
+            h, st = _layer_fwd(i, params, h, Kdim, pro, st, spec.bn_modules[i], spec.training, spec.rw, eps=spec.eps,
+                               special=fuse_sem if i == 5 else None)
+            Ys.append(h)
             states.append(st)
-            h, kin, pro = Y, N, K.PRO_ENC
+            pro = K.PRO_ENC
+        kin = h.shape[1]
         C = W8.shape[0]
         pp = torch.empty(M, C, device=dev)
         K.gemm(M, C, kin, h, kin, W8, W8.shape[1], pp, C, pro_a=K.PRO_ENC, pro_s=st.scale, pro_t=st.shift, bias=b8)
         if pool_ws is not None:
-            pooled, argidx = K.pool_finalize(pool_ws, M, Ws[5].shape[0], GR, states[5].scale, states[5].shift)
+            pooled, argidx = K.pool_finalize(pool_ws, M, Ys[5].shape[1], GR, states[5].scale, states[5].shift)
         else:
             pooled, argidx = K.pool_rows(Ys[5], GR, states[5].scale, states[5].shift)
         code = torch.empty(G, C, device=dev)
@@ -141,8 +196,6 @@ class PointEncoderFn(Function):
         GR = spec.group_rows
         G = M // GR
         dev = x.device
-        Ws = [params[4 * i].reshape(params[4 * i].shape[0], -1) for i in range(7)]
-        gs = [params[4 * i + 2] for i in range(7)]
         W8, fcW = params[28].reshape(params[28].shape[0], -1), params[30]
         C = W8.shape[0]
         grads = [None] * 32
@@ -163,30 +216,19 @@ class PointEncoderFn(Function):
                 pro=K.PRO_ENC, pro_s=states[6].scale, pro_t=states[6].shift)
         K.colsum(dpp, out=db8)
         grads[28], grads[29] = dW8.view(params[28].shape), db8
+
+        def sem_wgrad(dYi, cs, dW):   # semantic columns of fuse_sem
+            N, S, kin = dYi.shape[1], sem.shape[1], Ys[4].shape[1]
+            if spec.mode == "src":
+                # G-row GEMM on the per-group sums: short work
+                K.wgrad(_group_sums(dYi, cs, N, G, GR), N, sem, S, N, S, G, dW, dW.shape[1], out_off=kin)
+            else:
+                K.wgrad(dYi, N, sem, S, N, S, M, dW, dW.shape[1], out_off=kin)
+
         dY, Wn = dpp, W8   # gradient at the output of the layer above, and that layer's weight
         for i in range(6, -1, -1):
-            Y, st = Ys[i], states[i]
-            N = Y.shape[1]
-            Cn = dY.shape[1]
-            G_ = torch.empty(M, N, device=dev)
-            bws = torch.empty(K.nblocks(M), 2, N, device=dev)
-            kw = {}
-            if i == 5:
-                kw.update(pool_idx=argidx, pool_grad=dpool, pool_group_rows=GR)
-            # dH_i = dY_{i+1} @ W_{i+1}[:, :N]; fused ReLU mask + BN-backward partials of layer i
-            K.gemm(M, N, Cn, dY, Cn, Wn, Wn.shape[1], G_, N, b_kmajor=True, epi=K.EPI_BNBWD,
-                   Yp=Y, ldy=N, bn=st, bwd_res=False, bwd_ws=bws, **kw)
-            dgamma, dbeta = grad_buffer(gs[i]), grad_buffer(params[4 * i + 3])
-            coefs = K.bn_bwd_finalize(bws, M, N, gs[i], st.invstd, dgamma, dbeta, rw=spec.rw)
-            dYi, cs = K.bn_bwd_apply(G_, Y, False, st.mean, coefs, rw=spec.rw)
-            W = Ws[i]
-            dW, db = grad_buffer(params[4 * i]).view(W.shape), grad_buffer(params[4 * i + 1])
-            _enc_layer_wgrad(spec, i, N, M, G, GR, x, sem, Ys, states, dYi, cs, W, dW)
-            bias.add(cs, db)
-            grads[4 * i] = dW.view(params[4 * i].shape)
-            grads[4 * i + 1] = db
-            grads[4 * i + 2], grads[4 * i + 3] = dgamma, dbeta
-            dY, Wn = dYi, W
+            kw = dict(pool_idx=argidx, pool_grad=dpool, pool_group_rows=GR, special=sem_wgrad) if i == 5 else {}
+            dY, Wn = _layer_bwd(i, params, grads, bias, x, Ys, states, dY, Wn, K.ACT_ENC, K.PRO_ENC, spec.rw, **kw)
         bias.flush()
         return (None, None, None) + tuple(grads)
 
@@ -210,23 +252,6 @@ class _BiasSums:
         self.jobs = []
 
 
-def _enc_layer_wgrad(spec, i, N, M, G, GR, x, sem, Ys, states, dYi, cs, W, dW):
-    """Weight gradient of TargetEncoder layer i from its dY."""
-    if i == 0:
-        K.wgrad(dYi, N, x, 3, N, 3, M, dW, 3)
-    else:
-        Xp, stp = Ys[i - 1], states[i - 1]
-        kin = Xp.shape[1]
-        K.wgrad(dYi, N, Xp, kin, N, kin, M, dW, W.shape[1], pro=K.PRO_ENC, pro_s=stp.scale, pro_t=stp.shift)
-        if i == 5:   # semantic columns of fuse_sem
-            S = sem.shape[1]
-            if spec.mode == "src":
-                # G-row GEMM on the per-group sums: short work
-                K.wgrad(_group_sums(dYi, cs, N, G, GR), N, sem, S, N, S, G, dW, W.shape[1], out_off=kin)
-            else:
-                K.wgrad(dYi, N, sem, S, N, S, M, dW, W.shape[1], out_off=kin)
-
-
 def _group_sums(dY, cs, N, G, group_rows):
     """Per-group column sums of dY [G*group_rows, N]. When groups are whole 128-row blocks they
     come from the BN-backward apply's per-block partials cs [M/128, N] (8 MB instead of
@@ -236,18 +261,31 @@ def _group_sums(dY, cs, N, G, group_rows):
     return K.group_colsum(dY, N, G, group_rows=group_rows)
 
 
+class ResidualSpec(NamedTuple):
+    """Static description of one ResidualNetFn call.
+
+    code_first: True when the input is cat(code, pp) (recon_decoder_src)
+    grouping: gidx int32 [M] (row -> group) + off int32 [G+1], or fixed group_rows
+    bn_modules: the 3 BatchNorm1d modules (running stats updated in place when training)
+    rw: optional K.RowWeights (fixed group_rows only), as in EncoderSpec
+    """
+    code_first: bool
+    gidx: Any
+    off: Any
+    group_rows: int
+    training: bool
+    bn_modules: Any
+    rw: Any = None
+
+
 class ResidualNetFn(Function):
-    """re_residual_net on cat(per-point pp [M,Cp], group code [G,Cc]).
+    """re_residual_net on cat(per-point pp [M,Cp], group code [G,Cc]); spec: ResidualSpec.
 
     params: W1,b1,g1,be1, W2,b2,g2,be2, W3,b3,g3,be3, W4,b4 (14 tensors).
-    code_first: True when the input is cat(code, pp) (recon_decoder_src).
-    grouping: gidx int32 [M] (row -> group) + off int32 [G+1], or fixed group_rows.
-    rw: optional K.RowWeights (fixed group_rows only), as in EncoderSpec.
     """
 
     @staticmethod
     def forward(ctx, spec, pp, code, *params):
-        code_first, gidx, off, group_rows, training, bn_modules, rw = spec[:7]
         pp = pp.contiguous()
         code = code.contiguous()
         M, Cp = pp.shape
@@ -256,37 +294,28 @@ class ResidualNetFn(Function):
         W1 = params[0].reshape(params[0].shape[0], -1)
         ld1 = W1.shape[1]
         assert ld1 == Cp + Cc
-        pp_off, code_off = (Cc, 0) if code_first else (0, Cp)
+        pp_off, code_off = (Cc, 0) if spec.code_first else (0, Cp)
         N1 = W1.shape[0]
         rb = None
         if Cc > 0:   # the group half of the concatenated input becomes a per-group row bias
             rb = torch.empty(G, N1, device=dev)
             K.gemm(G, N1, Cc, code, Cc, W1, ld1, rb, N1, B_off=code_off)
+
+        def first(N):   # the pp columns of W1, the code half as the row bias
+            kw = dict(B_off=pp_off)
+            if rb is not None:
+                kw.update(rowbias=rb, ldr=N1, gidx=spec.gidx, group_rows=spec.group_rows)
+            return kw
+
         Ys, states = [], []
-        h, kin, pro, st = pp, Cp, K.PRO_NONE, None
+        h, pro, st = pp, K.PRO_NONE, None
         for i in range(3):
-            W = params[4 * i].reshape(params[4 * i].shape[0], -1)
-            N = W.shape[0]
-            Y = torch.empty(M, N, device=dev)
-            sws = torch.empty(K.nblocks(M), 2, N, device=dev)
-            kw = {}
-            if i == 0:
-                kw = dict(B_off=pp_off)
-                if rb is not None:
-                    kw.update(rowbias=rb, ldr=N1, gidx=gidx, group_rows=group_rows)
-            K.gemm(M, N, kin, h, h.shape[1], W, W.shape[1], Y, N, pro_a=pro,
-                   pro_s=None if st is None else st.scale, pro_t=None if st is None else st.shift,
-                   bias=params[4 * i + 1], epi=K.EPI_FWD, stat_ws=sws, stat_relu=True, **kw)
-            bnm = bn_modules[i]
-            if training:
-                st = K.bn_fwd_finalize(sws, M, N, params[4 * i + 2], params[4 * i + 3], BN_EPS,
-                                       bnm.momentum if bnm.momentum is not None else 0.0,
-                                       bnm.running_mean, bnm.running_var, rw=rw, num_batches_tracked=_nbt(bnm))
-            else:
-                st = K.bn_eval_state(params[4 * i + 2], params[4 * i + 3], bnm.running_mean, bnm.running_var, BN_EPS)
-            Ys.append(Y)
+            h, st = _layer_fwd(i, params, h, h.shape[1], pro, st, spec.bn_modules[i], spec.training, spec.rw,
+                               stat_relu=True, special=first if i == 0 else None)
+            Ys.append(h)
             states.append(st)
-            h, kin, pro = Y, N, K.PRO_RES
+            pro = K.PRO_RES
+        kin = h.shape[1]
         W4 = params[12].reshape(params[12].shape[0], -1)
         out = torch.empty(M, W4.shape[0], device=dev)
         K.gemm(M, W4.shape[0], kin, h, kin, W4, W4.shape[1], out, W4.shape[0], pro_a=K.PRO_RES,
@@ -297,8 +326,7 @@ class ResidualNetFn(Function):
 
     @staticmethod
     def backward(ctx, dout):
-        code_first, gidx, off, group_rows, training, bn_modules, rw = ctx.spec[:7]
-        states = ctx.states
+        spec, states = ctx.spec, ctx.states
         saved = ctx.saved_tensors
         pp, code = saved[:2]
         Ys = list(saved[2:5])
@@ -319,40 +347,24 @@ class ResidualNetFn(Function):
         dY, Wn = dout, W4
         W1 = params[0].reshape(params[0].shape[0], -1)
         ld1 = W1.shape[1]
-        pp_off, code_off = (Cc, 0) if code_first else (0, Cp)
+        pp_off, code_off = (Cc, 0) if spec.code_first else (0, Cp)
         dcode = torch.zeros(G, Cc, device=dev)
-        for i in range(2, -1, -1):
-            Y, st = Ys[i], states[i]
-            N = Y.shape[1]
-            Cn = dY.shape[1]
-            G_ = torch.empty(M, N, device=dev)
-            bws = torch.empty(K.nblocks(M), 2, N, device=dev)
-            K.gemm(M, N, Cn, dY, Cn, Wn, Wn.shape[1], G_, N, b_kmajor=True, epi=K.EPI_BNBWD,
-                   Yp=Y, ldy=N, bn=st, bwd_res=True, bwd_ws=bws)
-            dgamma, dbeta = grad_buffer(params[4 * i + 2]), grad_buffer(params[4 * i + 3])
-            coefs = K.bn_bwd_finalize(bws, M, N, params[4 * i + 2], st.invstd, dgamma, dbeta, rw=rw)
-            dYi, cs = K.bn_bwd_apply(G_, Y, True, st.mean, coefs, rw=rw)
-            W = params[4 * i].reshape(params[4 * i].shape[0], -1)
-            dW, db = grad_buffer(params[4 * i]).view(W.shape), grad_buffer(params[4 * i + 1])
-            if i == 0:
-                K.wgrad(dYi, N, pp, Cp, N, Cp, M, dW, ld1, out_off=pp_off)
-                if Cc > 0:                     # G-row work on the per-group sums: short kernels
-                    if off is not None:
-                        D = K.group_colsum(dYi, N, G, off=off)
-                    else:
-                        D = _group_sums(dYi, cs, N, G, group_rows)
-                    K.wgrad(D, N, code, Cc, N, Cc, G, dW, ld1, out_off=code_off)
-                    # dcode = D @ W1[:, code cols]
-                    K.gemm(G, Cc, N, D, N, W1, ld1, dcode, Cc, b_kmajor=True, B_off=code_off)
+
+        def code_half(dYi, cs, dW):   # G-row work on the per-group sums: short kernels
+            if Cc == 0:
+                return
+            N = dYi.shape[1]
+            if spec.off is not None:
+                D = K.group_colsum(dYi, N, G, off=spec.off)
             else:
-                Xp, stp = Ys[i - 1], states[i - 1]
-                K.wgrad(dYi, N, Xp, Xp.shape[1], N, Xp.shape[1], M, dW, W.shape[1],
-                        pro=K.PRO_RES, pro_s=stp.scale, pro_t=stp.shift)
-            bias.add(cs, db)
-            grads[4 * i] = dW.view(params[4 * i].shape)
-            grads[4 * i + 1] = db
-            grads[4 * i + 2], grads[4 * i + 3] = dgamma, dbeta
-            dY, Wn = dYi, W
+                D = _group_sums(dYi, cs, N, G, spec.group_rows)
+            K.wgrad(D, N, code, Cc, N, Cc, G, dW, ld1, out_off=code_off)
+            # dcode = D @ W1[:, code cols]
+            K.gemm(G, Cc, N, D, N, W1, ld1, dcode, Cc, b_kmajor=True, B_off=code_off)
+
+        for i in range(2, -1, -1):
+            kw = dict(out_off=pp_off, special=code_half) if i == 0 else {}
+            dY, Wn = _layer_bwd(i, params, grads, bias, pp, Ys, states, dY, Wn, K.ACT_RES, K.PRO_RES, spec.rw, **kw)
         bias.flush()
         # input gradient dpp = dY1 @ W1[:, pp cols]
         dpp = torch.empty(M, Cp, device=dev)
@@ -398,23 +410,19 @@ class PointChainFn(Function):
         Ys, states = [], []
         h, pro, st = x, K.PRO_NONE, None
         pool_ws = None
+
+        def fused_pool(N):   # pooling partials fused into the last GEMM's epilogue
+            nonlocal pool_ws
+            pool_ws = torch.empty(K.nblocks(M), 4, N, device=dev)
+            return dict(pool_ws=pool_ws, group_rows=GR)
+
         for i in range(L):
-            W = params[4 * i].reshape(params[4 * i].shape[0], -1)
-            N = W.shape[0]
-            Y = torch.empty(M, N, device=dev)
-            sws = torch.empty(K.nblocks(M), 2, N, device=dev)
-            kw = {}
-            if i == L - 1 and spec.pool and GR % K.BM == 0:
-                pool_ws = torch.empty(K.nblocks(M), 4, N, device=dev)
-                kw.update(pool_ws=pool_ws, group_rows=GR)
-            K.gemm(M, N, W.shape[1], h, h.shape[1], W, W.shape[1], Y, N, pro_a=pro,
-                   pro_s=None if st is None else st.scale, pro_t=None if st is None else st.shift,
-                   bias=params[4 * i + 1], epi=K.EPI_FWD, stat_ws=sws, **kw)
-            spec_i = _LayerBN(spec, i)
-            st = _bn_state(spec_i, 0, sws, M, N, params[4 * i + 2], params[4 * i + 3])
-            Ys.append(Y)
+            fuse = i == L - 1 and spec.pool and GR % K.BM == 0
+            h, st = _layer_fwd(i, params, h, h.shape[1], pro, st, spec.bn_modules[i], spec.training, None,
+                               special=fused_pool if fuse else None)
+            Ys.append(h)
             states.append(st)
-            h, pro = Y, K.PRO_ENC
+            pro = K.PRO_ENC
         relu_last = spec.acts[-1] == K.ACT_ENC
         NL = Ys[-1].shape[1]
         pooled = argidx = None
@@ -449,55 +457,22 @@ class PointChainFn(Function):
         grads = [None] * (4 * L)
         use_pool = spec.pool and dpooled is not None and dpooled.numel() > 0
         use_act = spec.want_act and dact is not None and dact.numel() > 0
-        dY, Wn = None, None
         bias = _BiasSums()
+        # no GEMM feeds the last layer: K = 0 (its own Y stands in for both operands), the epilogue
+        # adds the pooled gradient at the winning rows and the activation's own gradient, masks,
+        # and reduces
+        dY = Wn = Ys[-1]
+        kw = dict(Kdim=0)
+        if use_pool:
+            kw.update(pool_idx=argidx, pool_grad=dpooled.contiguous(), pool_group_rows=GR)
+        if use_act:
+            kw.update(gadd=dact.contiguous(), ldg=dY.shape[1])
         for i in range(L - 1, -1, -1):
-            Y, st = Ys[i], states[i]
-            N = Y.shape[1]
-            G_ = torch.empty(M, N, device=dev)
-            bws = torch.empty(K.nblocks(M), 2, N, device=dev)
-            if i == L - 1:
-                # no GEMM feeds the last layer: K = 0, the epilogue adds the pooled gradient at
-                # the winning rows and the activation's own gradient, masks, and reduces
-                kw = {}
-                if use_pool:
-                    kw.update(pool_idx=argidx, pool_grad=dpooled.contiguous(), pool_group_rows=GR)
-                if use_act:
-                    dact = dact.contiguous()
-                    kw.update(gadd=dact, ldg=N)
-                K.gemm(M, N, 0, Y, N, Y, N, G_, N, b_kmajor=True, epi=K.EPI_BNBWD, Yp=Y, ldy=N, bn=st,
-                       bwd_res=spec.acts[i], bwd_ws=bws, **kw)
-            else:
-                Cn = dY.shape[1]
-                K.gemm(M, N, Cn, dY, Cn, Wn, Wn.shape[1], G_, N, b_kmajor=True, epi=K.EPI_BNBWD,
-                       Yp=Y, ldy=N, bn=st, bwd_res=spec.acts[i], bwd_ws=bws)
-            gamma = params[4 * i + 2]
-            dgamma, dbeta = grad_buffer(gamma), grad_buffer(params[4 * i + 3])
-            coefs = K.bn_bwd_finalize(bws, M, N, gamma, st.invstd, dgamma, dbeta)
-            dYi, cs = K.bn_bwd_apply(G_, Y, False, st.mean, coefs)
-            W = params[4 * i].reshape(params[4 * i].shape[0], -1)
-            dW = grad_buffer(params[4 * i]).view(W.shape)
-            if i == 0:
-                K.wgrad(dYi, N, x, Cin, N, Cin, M, dW, Cin)
-            else:
-                Xp, stp = Ys[i - 1], states[i - 1]
-                kin = Xp.shape[1]
-                K.wgrad(dYi, N, Xp, kin, N, kin, M, dW, kin, pro=K.PRO_ENC, pro_s=stp.scale, pro_t=stp.shift)
-            grads[4 * i] = dW.view(params[4 * i].shape)
-            grads[4 * i + 1] = bias.add(cs, grad_buffer(params[4 * i + 1]))
-            grads[4 * i + 2], grads[4 * i + 3] = dgamma, dbeta
-            dY, Wn = dYi, W
+            dY, Wn = _layer_bwd(i, params, grads, bias, x, Ys, states, dY, Wn, spec.acts[i], K.PRO_ENC, None, **kw)
+            kw = {}
         bias.flush()
         dx = None
         if ctx.needs_input_grad[1]:
             dx = torch.empty(M, Cin, device=dev)
             K.gemm(M, Cin, dY.shape[1], dY, dY.shape[1], Wn, Wn.shape[1], dx, Cin, b_kmajor=True)
         return (None, dx) + tuple(grads)
-
-
-class _LayerBN:
-    """Adapter: the BN bookkeeping of layer i of a ChainSpec in _bn_state's form."""
-    __slots__ = ("bn_modules", "training", "eps", "rw")
-
-    def __init__(self, spec, i):
-        self.bn_modules, self.training, self.eps, self.rw = [spec.bn_modules[i]], spec.training, BN_EPS, None

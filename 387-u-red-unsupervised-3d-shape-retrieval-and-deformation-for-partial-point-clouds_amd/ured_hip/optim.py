@@ -33,7 +33,6 @@ scalar only when it changes (call sync_lr() before replaying a captured step aft
 change). optimizer.state holds the flat moments and the per-parameter step counts under "flat".
 """
 import ctypes
-import os
 
 import torch
 
@@ -44,7 +43,6 @@ _P, _I, _F, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double
 _lib.register({"ured_adam_clip_step": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _F, _P, _P, _P, _I,
                                        _D, _D, _D, _D, _P, _P, _P]})
 
-_GRAD_VIEWS = os.environ.get("URED_GRAD_VIEWS", "1") == "1"     # A/B knob (tools/gpu_py_ab.sh)
 CHUNK = 8192          # elements per workgroup (never straddles a parameter)
 ALIGN = 16            # each parameter slice starts on a 64-B boundary
 
@@ -57,7 +55,7 @@ def _slot_view(t):
     """(parameter, its flat-gradient view shaped like t, optimizer) or None."""
     p = t if t._base is None else t._base
     slot = getattr(p, "_ured_gslot", None)
-    if not _GRAD_VIEWS or slot is None or p.numel() != t.numel() or not t.is_contiguous():
+    if slot is None or p.numel() != t.numel() or not t.is_contiguous():
         return None
     opt, o, n = slot
     if opt.flat_grad is None:

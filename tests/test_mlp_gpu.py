@@ -283,6 +283,24 @@ def test_residual_net_split(dev, code_first, ragged):
             check_grad(sd[k].grad, v.grad, k, {n: p.grad for n, p in sd.items()})
 
 
+@pytest.mark.parametrize("n", [128, 40])
+def test_residual_net_eval_mode(dev, n):
+    """Eval BN (running statistics) in the Conv->ReLU->BN chain: 2 groups of n rows."""
+    P, _, _, rn = _mods(dev)
+    Pr = P["recon_decoder_full"]
+    g = torch.Generator().manual_seed(13 + n)
+    pp = torch.randn(2 * n, 64, generator=g)
+    code = torch.randn(2, 64, generator=g)
+    feat = torch.cat([pp, code[torch.arange(2 * n) // n]], 1).unsqueeze(0)
+    with torch.no_grad():
+        rn.forward_split(pp.to(dev), code.to(dev), group_rows=n)     # one train step moves the running stats
+        ured_ref.residual_net(Pr, feat)
+        rn.eval()
+        out = rn.forward_split(pp.to(dev), code.to(dev), group_rows=n)
+        ref = ured_ref.residual_net(Pr, feat, training=False).squeeze(0)
+    close(out, ref, 2e-4, "out_eval")
+
+
 def test_residual_net_plain_forward(dev):
     P, _, _, rn = _mods(dev)
     g = torch.Generator().manual_seed(12)

@@ -47,32 +47,34 @@ def main():
     torch.manual_seed(11)
     step = TrainStep(cfg, db, dev)
     batch = batch_to_device(synthetic.make_batch(a.bs, a.points, 512, parts=4, seed=5), dev, 512)
-    # the first encoder layer's weight-gradient inputs and output, per run (ured_hip.mlp)
-    import ured_hip.mlp as umlp
-    real_lw = umlp._enc_layer_wgrad
+    # the first encoder layer's weight-gradient inputs and output, per run: the Kin = 3 wgrad of a
+    # chain's layer 0 (ured_hip.mlp._layer_bwd), told apart by its row count
+    from ured_hip import kernels
+    real_wgrad = kernels.wgrad
     layer0 = []
 
     pre_sync = os.environ.get("DET_SYNC") == "1"
 
-    def spy(spec, i, N, M, G, GR, x, sem, Ys, states, dYi, cs, W, dW):
-        if i == 0:
-            if pre_sync:
-                torch.cuda.synchronize()
-            pre = (x.clone(), dYi.clone())
-        real_lw(spec, i, N, M, G, GR, x, sem, Ys, states, dYi, cs, W, dW)
-        if i == 0:
-            if not (torch.equal(pre[0], x) and torch.equal(pre[1], dYi)):
-                print(f"layer-0 wgrad ({spec.mode}): inputs changed across the call")
-            got = dW.clone()
+    def spy(dY, ldd, X, ldx, Cout, Kin, Mrows, out, ldo, **kw):
+        if not (Kin == 3 and X.shape[1] == 3):
+            return real_wgrad(dY, ldd, X, ldx, Cout, Kin, Mrows, out, ldo, **kw)
+        tag = f"M={Mrows}"
+        if pre_sync:
             torch.cuda.synchronize()
-            again = torch.empty_like(dW)           # the same weight gradient, recomputed in isolation
-            real_lw(spec, i, N, M, G, GR, x, sem, Ys, states, dYi, cs, W, again)
-            torch.cuda.synchronize()
-            if not torch.equal(got, again):
-                print(f"layer-0 wgrad ({spec.mode}): in-step result != isolated recompute, "
-                      f"max |d| {(got - again).abs().max().item():.3e}")
-            layer0.append((spec.mode, x.clone(), dYi.clone(), cs.clone(), got))
-    umlp._enc_layer_wgrad = spy
+        pre = (X.clone(), dY.clone())
+        real_wgrad(dY, ldd, X, ldx, Cout, Kin, Mrows, out, ldo, **kw)
+        if not (torch.equal(pre[0], X) and torch.equal(pre[1], dY)):
+            print(f"layer-0 wgrad ({tag}): inputs changed across the call")
+        got = out.clone()
+        torch.cuda.synchronize()
+        again = torch.empty_like(out)           # the same weight gradient, recomputed in isolation
+        real_wgrad(dY, ldd, X, ldx, Cout, Kin, Mrows, again, ldo, **kw)
+        torch.cuda.synchronize()
+        if not torch.equal(got, again):
+            print(f"layer-0 wgrad ({tag}): in-step result != isolated recompute, "
+                  f"max |d| {(got - again).abs().max().item():.3e}")
+        layer0.append((tag, X.clone(), dY.clone(), got))
+    kernels.wgrad = spy
     grads, losses = [], []
     for r in range(3):
         if a.poison is not None and r > 0:
@@ -95,7 +97,7 @@ def main():
     for j in range(per):
         for r in (1, 2):
             a0, a1 = layer0[j], layer0[r * per + j]
-            diff = [nm for nm, u, v in zip(("x", "dY", "cs", "dW"), a0[1:], a1[1:]) if not torch.equal(u, v)]
+            diff = [nm for nm, u, v in zip(("x", "dY", "dW"), a0[1:], a1[1:]) if not torch.equal(u, v)]
             if diff:
                 print(f"layer-0 wgrad call {j} ({a0[0]}) run {r}: differs in {diff}")
     print("deterministic" if bad == 0 else f"{bad} gradient tensors differ")
