@@ -32,9 +32,13 @@ REFERENCE_READS = {
     "base_dir", "middle_name", "category", "num_source", "num_workers", "src_connectivity",
     # inference (engine/vis.py)
     "top_k",
+    # the dataset's partial view (dataset/partnet_dataset.py:73-78, shapenet_dataset.py): with
+    # "partial", the loaders rotate point_occ by random angles in [-10, 10] degrees iff this is set
+    # (engine/train.py add_partial -> ured_hip.occ.occlude(rotate=...))
+    "random_rot",
 }
 REFERENCE_UNREAD = {
-    "data_dir", "use_connectivity", "action", "input_channels", "random_rot", "pooling", "n_knn",
+    "data_dir", "use_connectivity", "action", "input_channels", "pooling", "n_knn",
     "lr_autodecoder", "part_latent_dim", "use_deformed_pc_consistency", "share_src_latent", "clip_vec",
 }
 EXTRA = {
@@ -43,7 +47,14 @@ EXTRA = {
     "log_every", "compute_connectivity", "src_connectivity_plane", "synthetic_targets", "differentiable_gather", "sync_bn", "loss_head", "dist_backend",
     # data parallel (engine/dp.py, engine/graph.py)
     "dp_bucket_mb", "dp_last_bucket_mb", "dp_force_collectives", "graph_inline_collectives",
+    # partial (occluded) view of every target next to the full one (default false: batches unchanged)
+    "partial",
 }
+
+# what a loader adds to each batch with "partial" (the reference dataset's points_occ,
+# points_occ_mask, ori_point_occ, plus the gathered labels and the transform back to the full frame);
+# the training step does not read them (the reference's partial branch is commented out)
+PARTIAL_KEYS = ("point_occ", "point_occ_mask", "ori_point_occ", "labels_occ", "tgt_sem_occ", "occ_mean", "occ_rot")
 
 TRAIN_REQUIRED = ("source_latent_dim", "target_latent_dim", "sem_latent_dim", "MAX_NUM_PARTS", "device",
                   "optimizer", "learning_rate", "weight_decay", "lr_stepsize", "lr_decay", "batch_size",

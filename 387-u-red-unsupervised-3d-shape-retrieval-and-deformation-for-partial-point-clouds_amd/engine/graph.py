@@ -58,6 +58,7 @@ import gc
 
 import torch
 
+from engine.config import PARTIAL_KEYS
 from ured_hip.collective import SegmentedCapture
 from ured_hip.ops import refresh_static
 
@@ -231,6 +232,8 @@ class GraphedStep:
         self.update_captures = getattr(self, "update_captures", 0) + 1
 
     def step(self, batch, epoch=0):
+        if PARTIAL_KEYS[0] in batch:         # the partial view is not an input of the step
+            batch = {n: v for n, v in batch.items() if n not in PARTIAL_KEYS}
         if not self.inner.cfg.get("unique_sources", True) and "src_unique" in batch:
             # every slot encoded: the distinct-part tables are not read (and not part of the key)
             batch = {n: v for n, v in batch.items() if n != "src_unique"}

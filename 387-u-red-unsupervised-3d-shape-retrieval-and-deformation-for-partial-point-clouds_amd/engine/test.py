@@ -12,6 +12,9 @@ working path is engine/vis.py:118-256, restated here batched and without host sy
   6. (optional) the residual-net score max_points sum|r| (vis.py:221-231), NDCG@40 of the
      retrieval scores against the pseudo-label rows (cal_retrieval_score, vis.py:207), and the
      retrieved meshes deformed with the target parts' boxes as default (vis.py:278-296)
+  7. (optional, cfg["partial"]) the same from a partial view of each target, generated on the
+     device (ured_hip.occ; the reference dataset's points_occ), with the chamfer also taken against
+     the complete target in its own frame: infer_partial
     python engine/test.py [config.json]       (default config/config_vis_test.json, the reference's
                                               inference schema read by engine/vis.py:29; its
                                               init_dm / init_re checkpoints are loaded as the
@@ -30,7 +33,7 @@ if os.path.dirname(_HERE) not in sys.path:
 
 from dataset import synthetic  # noqa: E402
 from dataset.dataset_utils import cal_retrieval_score, deform_vertices, get_shape  # noqa: E402
-from engine.train import batch_to_device, get_models, get_part  # noqa: E402
+from engine.train import add_partial, batch_to_device, get_models, get_part  # noqa: E402
 from loss.chamfer_loss import compute_cm_loss  # noqa: E402
 from train_utils.load_sources import load_sources  # noqa: E402
 from ured_hip.ops import refresh_static  # noqa: E402
@@ -84,6 +87,29 @@ def infer(models, db, batch, cfg, src_codes=None, relevance=None, meshes=None):
     if meshes is not None:
         r["vertices"], r["vertex_off"] = deform_vertices(meshes["vmats"], meshes["voff"], idx, params,
                                                          param_def, cfg["alpha"])
+    return r
+
+
+def partial_sub_batch(batch):
+    """The partial view of a loader batch (cfg["partial"]) as an infer() / GraphedInfer batch."""
+    return {"x": batch["point_occ"], "labels": batch["labels_occ"], "tgt_sem": batch["tgt_sem_occ"]}
+
+
+@torch.no_grad()
+def infer_partial(models, db, batch, cfg, src_codes=None, run=None, **kw):
+    """Retrieval + deformation from the partial view of `batch` (the keys a cfg["partial"] loader
+    adds, engine/train.py add_partial): infer() on (point_occ, labels_occ, tgt_sem_occ) — the
+    occluded, centred (and rotated) cloud is all the networks see; a part without a surviving point
+    is an empty slot (mask 0, retrieved -1) — and its dict plus
+      cd_full [B]: the deformed output mapped back to the full shape's frame (out @ occ_rot +
+                   occ_mean, the inverse of point_occ = (occ_rot @ (ori - mean)^T)^T) scored with the
+                   same unmasked chamfer against the complete target batch["x"].
+    `run` (optional): a GraphedInfer to replay instead of the eager infer(); its outputs are the
+    captured tensors."""
+    sub = partial_sub_batch(batch)
+    r = dict(run(sub, **kw) if run is not None else infer(models, db, sub, cfg, src_codes, **kw))
+    full = torch.baddbmm(batch["occ_mean"].unsqueeze(1), r["out"], batch["occ_rot"])
+    r["cd_full"] = compute_cm_loss(full, batch["x"], r["mask"], batch_reduction=None)
     return r
 
 
@@ -149,7 +175,13 @@ def main(cfg):
     for i in range(int(cfg.get("iters_per_epoch", 2))):
         b = synthetic.make_batch(cfg["batch_size"], cfg.get("num_points", 2048), db.num_sources,
                                  max_parts=cfg["MAX_NUM_PARTS"], parts=cfg.get("parts", 4), seed=10_000 + i)
-        r = infer(models, db, batch_to_device(b, device), cfg, codes)
+        bd = batch_to_device(b, device)
+        if cfg.get("partial"):
+            r = infer_partial(models, db, add_partial(bd, cfg, cfg.get("seed", 0), 0, i), cfg, codes)
+            print(i, "cd", r["cd"].mean().item(), "cd_full", r["cd_full"].mean().item(),
+                  "retrieved[0]", r["retrieved"][0].tolist())
+            continue
+        r = infer(models, db, bd, cfg, codes)
         print(i, "cd", r["cd"].mean().item(), "retrieved[0]", r["retrieved"][0].tolist())
 
 

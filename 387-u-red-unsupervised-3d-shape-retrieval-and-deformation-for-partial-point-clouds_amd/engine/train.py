@@ -38,7 +38,7 @@ if os.path.dirname(_HERE) not in sys.path:
     sys.path.insert(0, os.path.dirname(_HERE))
 
 from dataset import synthetic  # noqa: E402
-from engine.config import check_config  # noqa: E402
+from engine.config import PARTIAL_KEYS, check_config  # noqa: E402
 from dataset.dataset_utils import (get_shape, get_shape_src, get_source_info, get_source_points,  # noqa: E402
                                    get_symmetric)
 from loss.basic_consistency_loss import compute_pc_consistency, compute_pc_consistency_weighted  # noqa: E402
@@ -393,6 +393,23 @@ def batch_to_device(b, device, num_sources=None, bucket=None):
     return out
 
 
+def add_partial(batch, cfg, seed, epoch, it):
+    """cfg["partial"]: the partial view the reference's datasets return with every item
+    (partnet_dataset.py:45-78: gen_occ_point, centring, rotation iff cfg["random_rot"]) added to a
+    device batch as PARTIAL_KEYS, generated on the device on the current stream (one launch,
+    ured_hip.occ.occlude) from (loader seed, epoch, iteration). No CPU path."""
+    from ured_hip.occ import occlude
+    if not batch["x"].is_cuda:
+        raise RuntimeError('"partial": the partial clouds are generated on the GPU only (device '
+                           f'{batch["x"].device}); there is no CPU fallback')
+    r = occlude(batch["x"], batch["labels"], batch["tgt_sem"], seed=seed, step=(int(epoch) << 32) | int(it),
+                rotate=bool(cfg.get("random_rot", False)))
+    batch.update(point_occ=r["point_occ"], point_occ_mask=r["mask"], ori_point_occ=r["ori_point_occ"],
+                 labels_occ=r["labels_occ"], tgt_sem_occ=r["sem_occ"], occ_mean=r["occ_mean"], occ_rot=r["occ_rot"])
+    assert all(k in batch for k in PARTIAL_KEYS)
+    return batch
+
+
 def loader_batching(cfg):
     """(batch size, shuffle) of the training loader: cfg["batch_size"] and a shuffled order in
     "train" mode, else 2 and the dataset order (engine/train.py:160-165,174)."""
@@ -494,6 +511,7 @@ class PseudoLabelLoader:
 
     def __iter__(self):
         rng = np.random.Generator(np.random.PCG64([self.seed, self.epoch]))
+        epoch = self.epoch
         self.epoch += 1
         T = self.targets["x"].shape[0]
         order = rng.permutation(T) if self.shuffle else np.arange(T)
@@ -507,8 +525,9 @@ class PseudoLabelLoader:
             b = {"x": self.targets["x"][sel], "labels": self.targets["labels"][sel],
                  "tgt_sem": self.targets["tgt_sem"][sel], "src_labels": host.numpy().copy()}
             self.last_sel = sel
-            yield batch_to_device(b, self.device, self.db.num_sources,
+            out = batch_to_device(b, self.device, self.db.num_sources,
                                   bucket=8 if self.cfg.get("cuda_graph") else None)
+            yield add_partial(out, self.cfg, self.seed, epoch, i) if self.cfg.get("partial") else out
 
 
 class SyntheticLoader:
@@ -517,16 +536,20 @@ class SyntheticLoader:
     def __init__(self, cfg, num_sources, device, seed=0):
         self.cfg, self.ns, self.device, self.seed = cfg, num_sources, device, seed
         self.n = int(cfg.get("iters_per_epoch", 10))
+        self.epoch = 0
 
     def __len__(self):
         return self.n
 
     def __iter__(self):
+        epoch = self.epoch
+        self.epoch += 1
         for i in range(self.n):
             b = synthetic.make_batch(loader_batching(self.cfg)[0], self.cfg.get("num_points", 2048), self.ns,
                                      max_parts=self.cfg["MAX_NUM_PARTS"], parts=self.cfg.get("parts", 4),
                                      seed=self.seed * 100003 + i)
-            yield batch_to_device(b, self.device, self.ns, bucket=8 if self.cfg.get("cuda_graph") else None)
+            out = batch_to_device(b, self.device, self.ns, bucket=8 if self.cfg.get("cuda_graph") else None)
+            yield add_partial(out, self.cfg, self.seed, epoch, i) if self.cfg.get("partial") else out
 
 
 class _ScalarLog:

@@ -8,6 +8,7 @@
   optim    FlatAdam: per-module gradient clipping + Adam over flat buffers
   node     DeformNet graph-node GEMM / BatchNorm launches
   ops      device-side part building (segment sums, AABBs)
+  occ      partial (occluded) target clouds: ball / random / slice / part occlusion, centring, rotation
   losshead the step's loss head (chamfer families, contrastive, residual, reconstruction, weighted sum)
 """
-from . import _lib, attn, kernels, losshead, nn, node, ops, optim, syncbn  # noqa: F401
+from . import _lib, attn, kernels, losshead, nn, node, occ, ops, optim, syncbn  # noqa: F401

@@ -40,7 +40,7 @@ extern "C" {
 #define URED_EINVAL 1001
 
 /* Library identification: returns URED_ABI_VERSION. */
-#define URED_ABI_VERSION 9   /* 9: ured_attn_fwd_sets / ured_attn_bwd_sets, ured_get_shape_src_fwd / _bwd; 8: ured_nn_bwd_set; 7: ured_copy_batch; 6: ured_part_rows_bwd_add; 5: node BN SyncBN fields (stats_out/stats_in, sums_out/sums_in); ured_bn_stats et al. */
+#define URED_ABI_VERSION 10  /* 10: ured_occlude; 9: ured_attn_fwd_sets / ured_attn_bwd_sets, ured_get_shape_src_fwd / _bwd; 8: ured_nn_bwd_set; 7: ured_copy_batch; 6: ured_part_rows_bwd_add; 5: node BN SyncBN fields (stats_out/stats_in, sums_out/sums_in); ured_bn_stats et al. */
 int ured_abi_version(void);
 /* Thread-local message for the last failing call on this thread ("" if none). */
 const char* ured_last_error(void);
@@ -468,6 +468,28 @@ int ured_build_parts(const long long* labels, const float* x, int B, int N, int 
                      long long* perm, long long* inv_perm, int* gid, int* off, long long* counts,
                      long long* k, float* mask, long long* rank_of_label, unsigned char* present,
                      float* aabb, float* param_def, void* stream);
+
+/* Partial (occluded) target clouds (csrc/occ.hip; the reference's dataset/gen_occ_point.py, and the
+ * centring / random rotation of partnet_dataset.py:60-78) in one launch, one workgroup per sample:
+ * x [B,N,3], labels / sem int64 [B,N], 16 <= N <= 4096, K = N / 2 points kept ->
+ * mask int64 [B,K] (kept point indices, ascending), ori_point_occ [B,K,3] = x[mask], point_occ
+ * [B,K,3] = R (x[mask] - occ_mean), labels_occ / sem_occ int64 [B,K], occ_mean [B,3], occ_rot
+ * [B,3,3] (identity unless `rotate`), and the plan used: plan_i int32 [B,URED_OCC_PLAN_I] (mode
+ * 0 ball / 1 random / 2 slice / 3 part, ncenter, 8 centre indices, slice centre index, part probe
+ * index), plan_f [B,URED_OCC_PLAN_F] (slice direction, 3 angles in degrees). Randomness is a
+ * stateless Philox-4x32-10 hash of (seed, step, sample, stream, counter) (exact function: the
+ * header comment of csrc/occ.hip): the same arguments give the same bits on every call.
+ * modes int32 [B] (optional device array; -1 = draw) or mode_all (-1 = none, else 0..3 for every
+ * sample; not both) overrides the drawn mode; plan_i_in / plan_f_in (optional,
+ * together, without modes / mode_all) replace the whole drawn plan (indices are clamped into the sample). */
+#define URED_OCC_PLAN_I 12
+#define URED_OCC_PLAN_F 6
+int ured_occlude(const float* x, const long long* labels, const long long* sem, int B, int N,
+                 unsigned long long seed, unsigned long long step, const int* modes, int mode_all,
+                 const int* plan_i_in,
+                 const float* plan_f_in, int rotate, long long* mask, float* ori_point_occ, float* point_occ,
+                 long long* labels_occ, long long* sem_occ, float* occ_mean, float* occ_rot, int* plan_i,
+                 float* plan_f, void* stream);
 
 /* Several device-to-device copies in one launch (csrc/copy.hip): the HIP-graph step refreshes its
  * static input batch before each replay (engine/graph.py) with this instead of one blit per
