@@ -144,7 +144,9 @@ __global__ __launch_bounds__(LT) void cd_pair_prep_kernel(CdShape sh, const floa
 // full family's b-side sum over x. The last workgroup combines (fp64, fixed order):
 //   full_s = sum_a / (k_b NP) + sum_b / N,  part_s = (1/k_b) sum_{i<k_b} (a_i / NP + b_i / cnt_i)
 //   terms  = [mean_b full (h=0), mean_b part (h=0), mean_b full (h=1), mean_b part (h=1)].
-constexpr int CD_MAX_UNITS = 2 * 128 * 33;    // 2B (P+1) partial units staged in LDS (B <= 128, P <= 32)
+// 2B (P+1) partial units staged in LDS (B <= 128, P <= 32): the most the entry point takes; a
+// device whose per-workgroup LDS holds fewer takes only what fits (lds_room)
+constexpr int CD_MAX_UNITS = 2 * 128 * 33;
 
 __global__ __launch_bounds__(LT) void cd_pair_reduce_kernel(CdShape sh, const float* __restrict__ daf,
         const float* __restrict__ dbf, const float* __restrict__ dap, const float* __restrict__ dbp,
@@ -389,7 +391,7 @@ struct ContrastArgs {
     const long long* src_labels;             // [n]: -1 -> ignored row, else label = s_off + i
     float* inv;                              // [n + n_all] 1 / max(|row|, 1e-12)
     float* lse;                              // [n] log-sum-exp of each logits row
-    float* part;                             // [n] per-row loss
+    float* part;                             // [2n] per row: its loss, 1 if it counts (0: ignored)
     unsigned* counter;
     float* loss;                             // [1]
     const float* g;                          // backward: upstream gradient of the loss
@@ -451,9 +453,12 @@ __global__ __launch_bounds__(LT) void contrast_fwd_kernel(ContrastArgs a) {
     const bool valid = a.src_labels[i] != -1;
     URED_DBG_CHECK(!valid || (a.s_off + i >= 0 && a.s_off + i < a.n_all));   // the label's logit (LDS)
     if (t == 0) {
-        const float l = m + logf(se);
-        a.lse[i] = l;
-        st_agent(a.part + 2 * i, valid ? l - lg[a.s_off + i] : 0.f);
+        // the row's loss lse - logit[label] as log(se) - (logit[label] - max): when the label's
+        // logit is the largest, the loss is log(se) itself and not a difference of two numbers
+        // near `scale`, whose fp32 spacing (1e-6) would be all that is left of a loss of 1e-4
+        const float ls = logf(se);
+        a.lse[i] = m + ls;
+        st_agent(a.part + 2 * i, valid ? ls - (lg[a.s_off + i] - m) : 0.f);
         st_agent(a.part + 2 * i + 1, valid ? 1.f : 0.f);
     }
     if (!last_arrival(a.counter, gridDim.x)) return;
@@ -554,6 +559,27 @@ __global__ void assemble_bwd_kernel(AssembleArgs a) {
 
 }  // namespace
 
+// Dynamic LDS bytes a launch of `kernel` may ask for: the device's per-workgroup limit less the
+// kernel's static arrays. Both are read once per process (the limit per device; *fixed is the
+// caller's cache for this kernel, -1 before the first call). -1 when they cannot be read.
+static long long lds_room(const void* kernel, long long* fixed) {
+    constexpr int MAXDEV = 64;
+    static int limit[MAXDEV];                 // 0: not read yet
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV) return -1;
+    if (limit[dev] == 0) {
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || v <= 0) return -1;
+        limit[dev] = v;
+    }
+    if (*fixed < 0) {
+        hipFuncAttributes fa;
+        if (hipFuncGetAttributes(&fa, kernel) != hipSuccess) return -1;
+        *fixed = (long long)fa.sharedSizeBytes;
+    }
+    return (long long)limit[dev] - *fixed;
+}
+
 extern "C" {
 
 int ured_cd_pair_prep(const float* out, const float* x, const float* x_sorted, const long long* k,
@@ -563,7 +589,8 @@ int ured_cd_pair_prep(const float* out, const float* x, const float* x_sorted, c
     URED_REQUIRE(B > 0 && S > 0 && N > 0 && P > 0 && NP > 0 && S >= P * NP, "ured_cd_pair_prep: bad sizes");
     URED_REQUIRE(out && x && x_sorted && k && counts && off && A && X2 && XS2 && segs_full && segs_part,
                  "ured_cd_pair_prep: null pointer");
-    const long long tot = 2LL * B * S > 2LL * B * N ? 2LL * B * S : 2LL * B * N;
+    long long tot = 2LL * B * S > 2LL * B * N ? 2LL * B * S : 2LL * B * N;
+    if (2LL * B * (P + 1) > tot) tot = 2LL * B * (P + 1);      // the segment tables' rows (NP == 1, N < P)
     hipLaunchKernelGGL(cd_pair_prep_kernel, dim3((unsigned)((tot + LT - 1) / LT)), dim3(LT), 0, (hipStream_t)stream,
                        CdShape{B, S, N, P, NP}, out, x, x_sorted, k, counts, off, A, X2, XS2, segs_full, segs_part);
     return ured::launch_status("ured_cd_pair_prep");
@@ -577,8 +604,12 @@ int ured_cd_pair_reduce(const float* dist_a_full, const float* dist_b_full, cons
                  "ured_cd_pair_reduce: bad sizes");
     URED_REQUIRE(dist_a_full && dist_b_full && dist_a_part && dist_b_part && k && counts && off && ws && counter && terms,
                  "ured_cd_pair_reduce: null pointer");
-    hipLaunchKernelGGL(cd_pair_reduce_kernel, dim3(P + 1, 2 * B), dim3(LT), (size_t)3 * 2 * B * (P + 1) * sizeof(float),
-                       (hipStream_t)stream,
+    const long long lds = 3LL * 2 * B * (P + 1) * (long long)sizeof(float);
+    static long long fixed = -1;              // the kernel's static LDS
+    URED_REQUIRE(lds <= lds_room(reinterpret_cast<const void*>(cd_pair_reduce_kernel), &fixed),
+                 "ured_cd_pair_reduce: 2B(P+1) = %d units (%lld bytes) do not fit the device's LDS per workgroup",
+                 2 * B * (P + 1), lds);
+    hipLaunchKernelGGL(cd_pair_reduce_kernel, dim3(P + 1, 2 * B), dim3(LT), (size_t)lds, (hipStream_t)stream,
                        CdShape{B, S, N, P, NP}, dist_a_full, dist_b_full, dist_a_part, dist_b_part, k, counts, off, ws,
                        counter, terms);
     return ured::launch_status("ured_cd_pair_reduce");
@@ -666,9 +697,12 @@ int ured_contrast_fwd(const float* t, const float* s_all, const long long* src_l
                  "ured_contrast_fwd: C %% 4 == 0 and 16-byte aligned rows required", C);
     ContrastArgs a = contrast_args(n, n_all, C, s_off, scale, t, s_all, src_labels, inv, lse);
     a.part = ws; a.counter = counter; a.loss = loss;
+    const long long lds = ((long long)C + n_all) * (long long)sizeof(float);
+    static long long fixed = -1;              // the kernel's static LDS
+    URED_REQUIRE(lds <= lds_room(reinterpret_cast<const void*>(contrast_fwd_kernel), &fixed),
+                 "ured_contrast_fwd: C %d + n_all %d floats do not fit the device's LDS per workgroup", C, n_all);
     hipLaunchKernelGGL(contrast_norms_kernel, dim3(n + n_all), dim3(LT), 0, (hipStream_t)stream, a);
-    const size_t lds = (size_t)(C + n_all) * sizeof(float);
-    hipLaunchKernelGGL(contrast_fwd_kernel, dim3(n), dim3(LT), lds, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(contrast_fwd_kernel, dim3(n), dim3(LT), (size_t)lds, (hipStream_t)stream, a);
     return ured::launch_status("ured_contrast_fwd");
 }
 
@@ -679,11 +713,16 @@ int ured_contrast_bwd(const float* t, const float* s_all, const long long* src_l
     URED_REQUIRE(n > 0 && n_all >= n && C > 0 && s_off >= 0 && s_off + n <= n_all && n_all <= CT_MAXN,
                  "ured_contrast_bwd: bad sizes");
     URED_REQUIRE(t && s_all && src_labels && inv && lse && g && dt, "ured_contrast_bwd: null pointer");
+    URED_REQUIRE(C % 4 == 0 && (((uintptr_t)t | (uintptr_t)s_all) & 15) == 0,
+                 "ured_contrast_bwd: C %% 4 == 0 and 16-byte aligned rows required");
     ContrastArgs a = contrast_args(n, n_all, C, s_off, scale, t, s_all, src_labels, const_cast<float*>(inv),
                                    const_cast<float*>(lse));
     a.g = g; a.dt = dt; a.ds = ds;
-    const size_t lds = (size_t)(2 * C + (n > n_all ? n : n_all)) * sizeof(float);
-    hipLaunchKernelGGL(contrast_bwd_kernel, dim3(n + (ds ? n : 0)), dim3(LT), lds, (hipStream_t)stream, a);
+    const long long lds = (2LL * C + n_all) * (long long)sizeof(float);      // n <= n_all
+    static long long fixed = -1;              // the kernel's static LDS
+    URED_REQUIRE(lds <= lds_room(reinterpret_cast<const void*>(contrast_bwd_kernel), &fixed),
+                 "ured_contrast_bwd: 2 C %d + n_all %d floats do not fit the device's LDS per workgroup", C, n_all);
+    hipLaunchKernelGGL(contrast_bwd_kernel, dim3(n + (ds ? n : 0)), dim3(LT), (size_t)lds, (hipStream_t)stream, a);
     return ured::launch_status("ured_contrast_bwd");
 }
 

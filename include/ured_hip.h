@@ -511,7 +511,9 @@ int ured_copy_batch(const UredCopyItem* items, int n, void* stream);
  *   reduce : the four scalars [full, part, mirror full, mirror part] from the two families' NN
  *            distances (dist_a_* [2B*S], dist_b_* [2B*N]); CD = mean(cost1) + mean(cost2), part
  *            CD = mean over the sample's parts, both averaged over B. ws: 3*2B*(P+1) floats;
- *            counter: a device uint that is 0 before the launch (it is left at 0);
+ *            counter: a device uint that is 0 before the launch (it is left at 0); 2B <= 256 and
+ *            2B(P+1) <= 8448, less where the device's LDS per workgroup cannot stage the
+ *            workspace (the call is then refused, nothing is launched);
  *   grad   : d terms g4 [4] -> the per-distance upstream weights of ured_nn_seg_bwd (gid int32
  *            [B*N]: part slot of each sorted row) and ga [2B*S*3] zeroed for its accumulation;
  *   fold   : grad_out [B,S,3] = ga[:B] + mirror(ga[B:]).
@@ -533,7 +535,13 @@ int ured_cd_pair_fold(const float* ga, int B, int S, float* grad_out, void* stre
  * compute_pc_consistency(rec, x) and compute_pc_consistency_weighted(recon_src, src_points, mask)
  * (loss/basic_consistency_loss.py:4-22), the last over the U distinct source parts of the batch
  * (recu / ptsu [U,NP,3]; slot r of the R = B*P part slots holds part inv[r], weight mask[r]).
- * Forward -> terms [4]; backward: upstream g4 [4] -> dres, drec [B,N,3], drecu [U,NP,3]. */
+ * Forward -> terms [4]; backward: upstream g4 [4] -> dres, drec [B,N,3], drecu [U,NP,3].
+ * ws: 3 * (ceil(B*N / 256) + U) floats. knn is not checked: it must lie in [0, S).
+ * A call with U == 0 (R, recu, ptsu, inv, mask, drecu unused) returns terms 0-2 and dres / drec
+ * as usual and terms[3] = nan, the reference's 0/0 of an empty weighted mean; so does a mask
+ * that sums to 0, and then every row of drecu is nan as well (autograd's too, but for the rows
+ * of a part that no slot refers to, which it leaves at 0). A part that no slot refers to, or
+ * only masked slots, adds nothing to terms[3] and gets drecu rows of 0. */
 typedef struct {
     int B, N, S, U, NP, R;
     const float* x; const float* out; const int* knn; const float* res; const float* rec;
@@ -547,7 +555,11 @@ int ured_point_losses_bwd(const UredPointLossDesc* d, const float* g4, float* dr
  * s_all [n_all,C] source codes of every rank (this rank's rows start at s_off), src_labels int64
  * [n] (-1: row ignored, else its label is s_off + i); loss = CE(scale * norm(t) norm(s_all)^T).
  * Forward writes inv norms [n + n_all], lse [n], ws [2n] and loss [1]; backward (g: d loss)
- * writes dt [n,C] and, when ds is not NULL, ds [n,C] for this rank's rows. */
+ * writes dt [n,C] and, when ds is not NULL, ds [n,C] for this rank's rows (the other ranks' rows
+ * of s_all are constants). Both need C % 4 == 0, 16-byte aligned t and s_all, n_all <= 4096 and
+ * C + n_all (backward: 2C + n_all) floats within the device's LDS per workgroup; a call outside
+ * that is refused and launches nothing. A batch whose rows are all ignored returns loss = nan
+ * (0/0, as F.cross_entropy does) and dt = ds = 0. */
 int ured_contrast_fwd(const float* t, const float* s_all, const long long* src_labels, int n, int n_all, int C,
                       int s_off, float scale, float* inv, float* lse, float* ws, unsigned* counter, float* loss,
                       void* stream);
