@@ -909,6 +909,9 @@ __global__ __launch_bounds__(256) void get_shape_src_bwd_kernel(const float* __r
 
 }  // namespace
 
+// K nearest neighbours (ured_knn_fwd / ured_knn_bwd): same code object, same sqd(), same debug word
+#include "knn.h"
+
 extern "C" {
 
 int ured_abi_version(void) { return URED_ABI_VERSION; }

@@ -44,6 +44,7 @@
 #include <hip/hip_runtime.h>
 #define URED_DBG_FILE 11
 #include "ured_common.h"
+#include "bitonic.h"
 #include "../../include/ured_hip.h"
 
 namespace {
@@ -71,36 +72,9 @@ __device__ __forceinline__ u32 occ_word(u64 seed, u64 step, u32 sample, u32 stre
 __device__ __forceinline__ float occ_unif(u32 r) { return (float)(r >> 8) * 5.9604644775390625e-8f; }
 __device__ __forceinline__ int occ_index(u32 r, int n) { return (int)(((u64)r * (u64)n) >> 32); }
 
-// the waves of a block each at their own pace: orders a wave's LDS writes before its later reads
-__device__ __forceinline__ void occ_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// ascending bitonic sort of keys[0, P2), P2 a power of two; every thread of the block calls it.
-// Thread t owns compare-exchange pair p = t (+ OC_T ...) of each stage: elements i and i | j with
-// i = p's bits above j shifted up by one. For j <= 64 the 64 pairs of a wave lie in one 128-element
-// block of their own; a stage with j > 64 reads and writes across those blocks. So a block-wide
-// barrier follows every stage whose own distance or whose successor's exceeds 64 (15 of the 66
-// stages at 2048 keys); between two stages with j <= 64 the wave alone is synchronised.
-__device__ void occ_sort(u64* keys, int P2, int t) {
-    __syncthreads();
-    const int half = P2 >> 1;
-    for (int k = 2; k <= P2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int p = t; p < half; p += OC_T) {
-                const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1)), q = i | j;
-                URED_DBG_CHECK(q < P2);
-                const u64 a = keys[i], b = keys[q];
-                if ((a > b) == ((i & k) == 0)) { keys[i] = b; keys[q] = a; }
-            }
-            const int next_j = j > 1 ? (j >> 1) : k;       // the next stage's distance (k: of 2k's first)
-            if (j > 64 || next_j > 64) __syncthreads(); else occ_wave_sync();
-        }
-    }
-    __syncthreads();
-}
+// ascending bitonic sort of keys[0, P2), P2 a power of two; every thread of the block calls it
+// (bitonic.h: the block-wide sort shared with the K-nearest-neighbour selection)
+__device__ __forceinline__ void occ_sort(u64* keys, int P2, int t) { ured::bitonic_sort_u64<OC_T>(keys, P2, t); }
 
 __global__ __launch_bounds__(OC_T) void occlude_kernel(const float* __restrict__ x, const long long* __restrict__ labels,
         const long long* __restrict__ sem, int N, u64 seed, u64 step, const int* __restrict__ modes,

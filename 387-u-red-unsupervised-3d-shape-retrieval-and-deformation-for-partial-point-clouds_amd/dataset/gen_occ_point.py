@@ -35,3 +35,20 @@ def generate_occ_point_random(points, seed=0, step=0):
 
 def generate_occ_point_part(points, semantics, seed=0, step=0):
     return _forced(points, _occ.MODE_PART, seed, step, semantics)
+
+
+def neighbour_table(points):
+    """The `dis_mat` table the reference's ball occlusion builds and caches per target
+    (gen_occ_point.py:31-33: knn_points(points, points, K=N // 2, return_sorted=True).idx): for
+    every point the indices of its N // 2 nearest points of the same cloud (itself first, unless
+    a duplicate with a lower index precedes it), ascending in (distance, index). points [N,3] or
+    [B,N,3] on the device, N <= 4096 -> int64 [..., N, N // 2]. The occlusion kernel does not need
+    the table; it is for sharing caches with the reference pipeline."""
+    from ured_hip import nn as _nn
+    single = points.dim() == 2
+    x = points.unsqueeze(0) if single else points
+    N = x.shape[1]
+    if N < 2 or N > _nn.KNN_SEL_M:
+        raise ValueError(f"neighbour_table: N {N} outside [2, {_nn.KNN_SEL_M}]")
+    idx = _nn.knn(x.detach(), x.detach(), N // 2)[1].long()
+    return idx[0] if single else idx

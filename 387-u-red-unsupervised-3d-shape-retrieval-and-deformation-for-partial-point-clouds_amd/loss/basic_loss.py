@@ -1,28 +1,47 @@
 """Drop-in for the reference loss/basic_loss.py: residual_retrieval_loss (basic_loss.py:249-265)
-and a pytorch3d.ops.knn_points(K=1) subset.
+and a stand-in for pytorch3d.ops.knn_points.
 
-pytorch3d is absent from the reference tree (version unpinned); the K=1 query
-here is the x -> source direction of the same HIP nearest-neighbour primitive
-(squared L2, lowest index on ties), one ragged launch for the whole batch.
+pytorch3d is absent from the reference tree (version unpinned, not importable here: the
+semantics are taken from its documented contract and the boundary stays parity-unpinned); the
+K=1 query here is the x -> source direction of the same HIP nearest-neighbour primitive
+(squared L2, lowest index on ties), one ragged launch for the whole batch; K > 1 is
+ured_hip.nn.knn (the same distance, the same tie rule).
 """
 from collections import namedtuple
 
 import torch
 
-from ured_hip.nn import nn_segments
+from ured_hip.nn import knn, nn_segments
 
 NP_PER_PART = 1024
 KNN = namedtuple("KNN", ["dists", "idx", "knn"])
 
 
-def knn_points(p1, p2, lengths1=None, lengths2=None, K=1, return_nn=False, **_):
-    """K=1 nearest neighbour of every p1 point among p2 (pytorch3d.ops.knn_points subset).
+def knn_points(p1, p2, lengths1=None, lengths2=None, norm=2, K=1, version=-1, return_nn=False,
+               return_sorted=True, **_):
+    """The K nearest neighbours of every p1 point among p2 (pytorch3d.ops.knn_points).
 
-    p1 [B,n,3], p2 [B,m,3]; lengths2 [B] limits the valid p2 points per sample.
-    Returns dists [B,n,1] (squared), idx [B,n,1] (int64), knn [B,n,1,3] if return_nn.
+    p1 [B,n,3], p2 [B,m,3]; lengths1 / lengths2 [B] limit the valid points per sample.
+    Returns dists [B,n,K] (squared L2), idx [B,n,K] (int64), knn [B,n,K,3] if return_nn, sorted by
+    (distance, index) whatever `return_sorted` says (False permits any order); padded slots
+    (beyond lengths2, rows beyond lengths1) hold 0. `version` selects among pytorch3d's kernels
+    and has no meaning here. 1 <= K <= 1024; K > 32 needs m <= 4096 (ured_hip.nn.knn).
     """
+    if norm != 2:
+        raise NotImplementedError("only norm=2 (squared L2) is implemented")
     if K != 1:
-        raise NotImplementedError("only K=1 is on the U-RED path (loss/basic_loss.py:257)")
+        dev = p1.device
+        l1 = None if lengths1 is None else lengths1.to(dev)
+        l2 = None if lengths2 is None else lengths2.to(dev)
+        d, i = knn(p1, p2, K, l1, l2)
+        i = i.long()
+        nn = None
+        if return_nn:
+            B, n, _ = p1.shape
+            nn = torch.gather(p2, 1, i.reshape(B, n * K, 1).expand(-1, -1, 3)).view(B, n, K, 3)
+            if l2 is not None:       # padded slots read 0, as pytorch3d's knn_gather leaves them
+                nn = nn * (torch.arange(K, device=dev) < l2.view(B, 1, 1)).unsqueeze(-1)
+        return KNN(d, i, nn)
     B, n, _ = p1.shape
     m = p2.shape[1]
     dev = p1.device

@@ -1,7 +1,9 @@
 """ured_hip — the MI355X (gfx950) hot path of U-RED on libured_hip.so.
 
   _lib     ctypes loader of the C-ABI (include/ured_hip.h); raises if missing
-  nn       nearest-neighbour / chamfer autograd ops (dense + ragged segments)
+  nn       nearest-neighbour / chamfer autograd ops (dense + ragged segments) and knn(): the K
+           nearest neighbours, 1 <= K <= 1024, sorted by (distance, index), with valid lengths
+           (the stand-in for pytorch3d.ops.knn_points: parity-unpinned, semantics from its docs)
   kernels  typed wrappers of the fused per-point MLP entry points
   mlp      PointEncoderFn / ResidualNetFn / PointChainFn autograd chains
   attn     graph-node multi-head attention (DeformNet's GraphAttentionNet core)

@@ -166,6 +166,73 @@ def nn_segments(a, b, segs, max_a, max_b, dirs=3):
     return da.view(a_shape), ia.view(a_shape), db.view(b_shape), ib.view(b_shape)
 
 
+KNN_SEL_M = 4096          # KNN_SEL_M (csrc/knn.h): the most p2 points for K > 32
+
+
+def _as_lengths(t, b, name, dev):
+    if t is None:
+        return None
+    if not torch.is_tensor(t) or t.dtype.is_floating_point or t.dtype == torch.bool or t.dim() != 1 or t.shape[0] != b:
+        raise ValueError(f"{name}: expected an integer tensor of shape [{b}]")
+    _lib.require_device(t)
+    if t.device != dev:
+        raise ValueError(f"{name}: on {t.device}, the points on {dev}")
+    return t.to(torch.int32).contiguous()      # a device cast: no host read
+
+
+class KNNFunction(Function):
+    """(p1 [b,n,3], p2 [b,m,3], K, lengths1, lengths2) -> (dists [b,n,K], idx [b,n,K] i32);
+    see ured_knn_fwd / ured_knn_bwd in include/ured_hip.h."""
+
+    @staticmethod
+    def forward(ctx, p1, p2, K, lengths1, lengths2):
+        p1 = _as_points(p1, "p1")
+        p2 = _as_points(p2, "p2")
+        _lib.require_device(p1, p2)
+        if p1.dim() != 3 or p2.dim() != 3 or p1.shape[0] != p2.shape[0]:
+            raise ValueError(f"expected [b,n,3] and [b,m,3], got {tuple(p1.shape)} {tuple(p2.shape)}")
+        if p1.device != p2.device:
+            raise ValueError(f"p1 on {p1.device}, p2 on {p2.device}")
+        b, n, _ = p1.shape
+        m = p2.shape[1]
+        K = int(K)
+        l1 = _as_lengths(lengths1, b, "lengths1", p1.device)
+        l2 = _as_lengths(lengths2, b, "lengths2", p1.device)
+        dists = torch.empty(b, n, max(K, 0), device=p1.device, dtype=torch.float32)
+        idx = torch.empty(b, n, max(K, 0), device=p1.device, dtype=torch.int32)
+        # the library checks K and the K / m limits before any device work (URED_EINVAL)
+        _lib.call("ured_knn_fwd", _lib.ptr(p1), _lib.ptr(p2), b, n, m, K, _lib.ptr(l1), _lib.ptr(l2),
+                  _lib.ptr(dists), _lib.ptr(idx), _lib.stream_of(p1))
+        ctx.save_for_backward(p1, p2, idx, l1, l2)
+        ctx.K = K
+        ctx.mark_non_differentiable(idx)
+        return dists, idx
+
+    @staticmethod
+    def backward(ctx, gd, _gi):
+        p1, p2, idx, l1, l2 = ctx.saved_tensors
+        b, n, _ = p1.shape
+        m = p2.shape[1]
+        if gd is None or b * (n + m) == 0:
+            return torch.zeros_like(p1), torch.zeros_like(p2), None, None, None
+        # both gradients in one allocation, every element written by the kernels (no zero fill)
+        gbuf = torch.empty(3 * b * (n + m), device=p1.device, dtype=p1.dtype)
+        g1, g2 = gbuf[:3 * b * n].view(b, n, 3), gbuf[3 * b * n:].view(b, m, 3)
+        gd = gd.contiguous()
+        _lib.call("ured_knn_bwd", _lib.ptr(p1), _lib.ptr(p2), b, n, m, ctx.K, _lib.ptr(l1), _lib.ptr(l2),
+                  _lib.ptr(gd), _lib.ptr(idx), _lib.ptr(g1), _lib.ptr(g2), _lib.stream_of(p1))
+        return g1, g2, None, None, None
+
+
+def knn(p1, p2, K, lengths1=None, lengths2=None):
+    """The K nearest p2 points of every p1 point: (dists [b,n,K] squared L2, idx [b,n,K] int32),
+    ascending in (distance, index); column 0 is bitwise nn_dense's dist1 / idx1. lengths1 /
+    lengths2 [b] (integer device tensors) limit the valid points per sample; slots beyond
+    lengths2 and rows beyond lengths1 hold dist 0, idx 0 and carry no gradient. 1 <= K <= 1024;
+    K > 32 needs m <= 4096. idx is not differentiable."""
+    return KNNFunction.apply(p1, p2, K, lengths1, lengths2)
+
+
 DCD_MAX_POINTS = 16384
 
 

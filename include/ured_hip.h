@@ -40,7 +40,7 @@ extern "C" {
 #define URED_EINVAL 1001
 
 /* Library identification: returns URED_ABI_VERSION. */
-#define URED_ABI_VERSION 10  /* 10: ured_occlude; 9: ured_attn_fwd_sets / ured_attn_bwd_sets, ured_get_shape_src_fwd / _bwd; 8: ured_nn_bwd_set; 7: ured_copy_batch; 6: ured_part_rows_bwd_add; 5: node BN SyncBN fields (stats_out/stats_in, sums_out/sums_in); ured_bn_stats et al. */
+#define URED_ABI_VERSION 11  /* 11: ured_knn_fwd / ured_knn_bwd; 10: ured_occlude; 9: ured_attn_fwd_sets / ured_attn_bwd_sets, ured_get_shape_src_fwd / _bwd; 8: ured_nn_bwd_set; 7: ured_copy_batch; 6: ured_part_rows_bwd_add; 5: node BN SyncBN fields (stats_out/stats_in, sums_out/sums_in); ured_bn_stats et al. */
 int ured_abi_version(void);
 /* Thread-local message for the last failing call on this thread ("" if none). */
 const char* ured_last_error(void);
@@ -97,6 +97,28 @@ int ured_nn_seg_fwd_ws(const float* a, const float* b, const int* segs, int nseg
                        int max_a_len, int max_b_len, int dirs, int a_total, int b_total,
                        float* dist_a, int* idx_a, float* dist_b, int* idx_b,
                        void* workspace, size_t ws_bytes, void* stream);
+
+/* K nearest neighbours (pytorch3d.ops.knn_points semantics; the reference's call sites are
+ * loss/basic_loss.py:257 with K = 1 and dataset/gen_occ_point.py:31-33 with K = N / 2).
+ * p1 [b,n,3] queries, p2 [b,m,3] refs -> dists [b,n,K], idx [b,n,K]: row i of sample b lists the
+ * min(K, len2) valid p2 points with the smallest (distance, index), ascending in that order
+ * (lowest index on ties), by the contract distance of ured_nn_fwd with the p1 point as the query;
+ * column 0 is bitwise dist1 / idx1 of ured_nn_fwd. lengths1 / lengths2: DEVICE int32 [b] numbers
+ * of valid points per sample (NULL = n / m), clamped into [0, n] / [0, m] on the device (no host
+ * read). Slots k >= len2 and every slot of a row i >= len1 are written as dist 0, idx 0.
+ * Limits: 1 <= K <= 1024; K <= 32: any m (one thread per query, the K best in registers);
+ * K > 32: m <= 4096 (one workgroup per query, a sort in LDS); K > m is allowed (padding);
+ * b <= 65535, n * K < 2^31. No workspace. */
+int ured_knn_fwd(const float* p1, const float* p2, int b, int n, int m, int K, const int* lengths1,
+                 const int* lengths2, float* dists, int* idx, void* stream);
+/* Its backward, WRITTEN as by ured_nn_bwd_set (every element of grad_p1 [b,n,3] and grad_p2
+ * [b,m,3] is set; rows beyond len1 and points beyond len2 get zeros). Over the valid slots, with
+ * g = grad_dists[b,i,k] and j = idx[b,i,k]:
+ *   grad_p1[b,i] = sum_k 2 g (p1_i - p2_j)        grad_p2[b,j] = - sum_{(i,k): idx = j} 2 g (p1_i - p2_j)
+ * Deterministic (gather form, (i,k) ascending), no atomics. */
+int ured_knn_bwd(const float* p1, const float* p2, int b, int n, int m, int K, const int* lengths1,
+                 const int* lengths2, const float* grad_dists, const int* idx, float* grad_p1, float* grad_p2,
+                 void* stream);
 
 /* get_shape (dataset/dataset_utils.py:691-726): out[j, r] = sum_k A[j, r, k] p[j, k] for every
  * part slot j (A [nparts, rows, 6] contiguous, 8-byte aligned; p [nparts, 6] = weight*param +
