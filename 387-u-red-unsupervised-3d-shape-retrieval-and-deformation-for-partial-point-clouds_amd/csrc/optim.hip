@@ -64,7 +64,9 @@ __global__ __launch_bounds__(256) void seg_coef_kernel(const double* __restrict_
     }
     if (t == 0) {
         const float norm = (float)sqrt(red[0]);
-        coef[s] = max_norm > 0.f ? fminf(max_norm / (norm + 1e-6f), 1.f) : 1.f;
+        // torch's clamp(max=1): a nan norm stays nan (fminf would return the 1), an infinite one gives 0
+        const float c = max_norm / (norm + 1e-6f);
+        coef[s] = max_norm > 0.f ? (c > 1.f ? 1.f : c) : 1.f;
     }
     if (s == 0)
         for (int i = t; i < n_active; i += 256) param_step[active_params[i]] += 1.f;

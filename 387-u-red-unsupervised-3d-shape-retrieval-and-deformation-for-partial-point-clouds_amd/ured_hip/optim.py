@@ -27,7 +27,8 @@ fresh gradient tensors and the gather is one copy.
 
 Semantics kept: after step() (and after gather_grads(), which engine/dp.py calls before its
 all-reduce of the flat gradient) `p.grad` of every active parameter is a view of the flat
-gradient and holds the clipped gradient (clip_grad_norm_ scales in place); the learning rate is
+gradient and holds the clipped gradient (clip_grad_norm_ scales in place; a nan norm makes the
+module's coefficient, gradients and parameters nan as it does there); the learning rate is
 read from param_groups[0]["lr"] on every step (StepLR works unchanged) and copied to a device
 scalar only when it changes (call sync_lr() before replaying a captured step after an lr
 change). optimizer.state holds the flat moments and the per-parameter step counts under "flat".

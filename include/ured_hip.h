@@ -260,7 +260,8 @@ int ured_gemm(const UredGemmDesc* d, void* stream);
  * parameters that take this step are listed (those with a gradient: torch's clip_grad_norm_
  * and Adam skip the others). max_norm > 0: per-segment L2 norm (fp64 chunk partials in
  * `partial`, fixed order) -> coef[s] = min(max_norm / (norm + 1e-6), 1), gradient scaled in
- * place; max_norm <= 0: no clipping. param_step[active_params[i]] (device, one step count per
+ * place; a non-finite norm propagates as in clip_grad_norm_ (nan norm -> nan coefficient, so
+ * the whole segment becomes nan; infinite norm -> 0); max_norm <= 0: no clipping. param_step[active_params[i]] (device, one step count per
  * parameter as in torch's Adam) is incremented for i < n_active, then every listed element takes
  * one Adam step with *lr (device) and its parameter's bias corrections. Deterministic. */
 int ured_adam_clip_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq,
