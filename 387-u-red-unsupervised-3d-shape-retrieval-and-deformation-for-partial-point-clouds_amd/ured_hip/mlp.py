@@ -90,6 +90,18 @@ def _layer_fwd(i, params, h, Kdim, pro, st, bnm, training, rw, *, eps=BN_EPS, st
     return Y, _bn_state(bnm, training, rw, sws, M, N, params[4 * i + 2], params[4 * i + 3], eps)
 
 
+def _require_training(spec, name):
+    """_layer_bwd applies the batch-statistics BN backward (the mean and variance terms of
+    bn_bwd_finalize / bn_bwd_apply). A chain that ran on running statistics (training=False) has
+    the eval-BN gradient instead, scale and mask only, which no chain kernel computes: refuse
+    rather than return the training formula. Inference runs under no_grad and never gets here
+    (the check sits in backward because forward cannot tell a no_grad call: ctx.needs_input_grad
+    is set either way)."""
+    if not spec.training:
+        raise RuntimeError(f"{name}: backward through a chain that ran with training=False (eval-mode BatchNorm) is "
+                           "not supported; run eval-mode chains under torch.no_grad()")
+
+
 def _layer_bwd(i, params, grads, bias, x, Ys, states, dY, Wn, act, pro, rw, *, Kdim=None, out_off=0, special=None,
                **kw):
     """Backward of layer i of a chain, from dY = the gradient at the output of the layer above
@@ -188,6 +200,7 @@ class PointEncoderFn(Function):
     @staticmethod
     def backward(ctx, dcode, dpp):
         spec, states = ctx.spec, ctx.states
+        _require_training(spec, "PointEncoderFn")
         saved = ctx.saved_tensors
         x, sem, pooled, argidx = saved[:4]
         Ys = list(saved[4:11])
@@ -327,6 +340,7 @@ class ResidualNetFn(Function):
     @staticmethod
     def backward(ctx, dout):
         spec, states = ctx.spec, ctx.states
+        _require_training(spec, "ResidualNetFn")
         saved = ctx.saved_tensors
         pp, code = saved[:2]
         Ys = list(saved[2:5])
@@ -446,6 +460,7 @@ class PointChainFn(Function):
     @staticmethod
     def backward(ctx, dpooled, dact):
         spec, states = ctx.spec, ctx.states
+        _require_training(spec, "PointChainFn")
         saved = ctx.saved_tensors
         L = len(spec.acts)
         x, argidx = saved[0], saved[1]
