@@ -28,6 +28,9 @@
  *   ured_node_gemm / ured_node_bn_fwd / ured_node_bn_bwd <- the graph-node Conv1d / BatchNorm1d
  *                       layers of DeformNet_MatchingNet (network/deformation_net.py:61,90,
  *                       attention_graph/attention_gnn.py:20-54, attention_utils.py:62-86).
+ *   ured_fps / ured_ball_query / ured_group_fwd / ured_group_bwd <- farthest_point_sample,
+ *                       query_ball_point, index_points + sample_and_group and their autograd
+ *                       (network/pointnet/pointnet2_utils.py:43-138).
  */
 #ifndef URED_HIP_H
 #define URED_HIP_H
@@ -40,7 +43,7 @@ extern "C" {
 #define URED_EINVAL 1001
 
 /* Library identification: returns URED_ABI_VERSION. */
-#define URED_ABI_VERSION 11  /* 11: ured_knn_fwd / ured_knn_bwd; 10: ured_occlude; 9: ured_attn_fwd_sets / ured_attn_bwd_sets, ured_get_shape_src_fwd / _bwd; 8: ured_nn_bwd_set; 7: ured_copy_batch; 6: ured_part_rows_bwd_add; 5: node BN SyncBN fields (stats_out/stats_in, sums_out/sums_in); ured_bn_stats et al. */
+#define URED_ABI_VERSION 12  /* 12: ured_fps / ured_ball_query / ured_group_fwd / ured_group_bwd; 11: ured_knn_fwd / ured_knn_bwd; 10: ured_occlude; 9: ured_attn_fwd_sets / ured_attn_bwd_sets, ured_get_shape_src_fwd / _bwd; 8: ured_nn_bwd_set; 7: ured_copy_batch; 6: ured_part_rows_bwd_add; 5: node BN SyncBN fields (stats_out/stats_in, sums_out/sums_in); ured_bn_stats et al. */
 int ured_abi_version(void);
 /* Thread-local message for the last failing call on this thread ("" if none). */
 const char* ured_last_error(void);
@@ -521,6 +524,42 @@ int ured_occlude(const float* x, const long long* labels, const long long* sem, 
 #define URED_COPY_MAX 16
 typedef struct { void* dst; const void* src; long long bytes; } UredCopyItem;
 int ured_copy_batch(const UredCopyItem* items, int n, void* stream);
+
+/* ---------------- set abstraction (csrc/group.hip) ---------------- */
+/* The sampling and grouping primitives of PointNet++ (network/pointnet/pointnet2_utils.py:63-138).
+ * Contract distance of all three: d = ((dx*dx) + (dy*dy)) + (dz*dz) in fp32, no FMA contraction.
+ *
+ * Farthest-point sampling (farthest_point_sample, :63-84). xyz [B,N,3], start DEVICE int32 [B]
+ * (clamped into [0,N) on the device, never read on the host) -> idx_out int32 [B,npoint].
+ * The reference's recurrence: dmin[j] starts at 1e10f; step i writes the current f to
+ * idx_out[b,i], sets dmin[j] = d wherever d < dmin[j] (d to point f), and the next f is the lowest
+ * index among the maxima of dmin. npoint > N is allowed (the recurrence stays defined).
+ * Limits: 1 <= N <= URED_FPS_NMAX (one workgroup per cloud holds the cloud in registers: 1024
+ * threads x 16 points), npoint >= 1, B <= 65535, B * npoint < 2^31. */
+#define URED_FPS_NMAX 16384
+int ured_fps(const float* xyz, const int* start, int B, int N, int npoint, int* idx_out, void* stream);
+/* Ball query (query_ball_point, :87-107). xyz [B,N,3], new_xyz [B,S,3] -> idx_out int32
+ * [B,S,nsample]: row s lists the first nsample indices j, ascending, with !(d(new_xyz[s], xyz[j])
+ * > r2) (inclusive boundary); a shorter row is padded with its first index; a row without a hit
+ * is N in every slot (the reference's value). Limits: N >= 1, nsample >= 1 (nsample > N is
+ * allowed), r2 >= 0, B <= 65535, B * S * nsample * 3 < 2^31, B * N * 3 < 2^31. */
+int ured_ball_query(const float* xyz, const float* new_xyz, int B, int N, int S, float r2, int nsample, int* idx_out,
+                    void* stream);
+/* Grouping (index_points + the centring and cat of sample_and_group, :122-134). idx int32 [B,S,K] ->
+ * out [B*S*K, C] point-major, C = 3 + D: columns 0..2 = xyz[b,idx] - new_xyz[b,s] (one fp32
+ * subtract), the rest = points[b,idx] (points [B,N,D]; NULL with D = 0). xyz and new_xyz may both
+ * be NULL: a plain gather, C = D. An index outside [0,N) (the ball query's N) gives a zero row.
+ * Limits: N, K >= 1, B <= 65535, B * S * K * (3 + D) < 2^31, B * N * max(D, 3) < 2^31. */
+int ured_group_fwd(const float* xyz, const float* new_xyz, const float* points, const int* idx, int B, int N, int S,
+                   int K, int D, float* out, void* stream);
+/* Its backward, WRITTEN (every element of grad_xyz [B,N,3], grad_new_xyz [B,S,3] and grad_points
+ * [B,N,D] is set): each element of grad_xyz / grad_points is the fp32 sum of its (s,k)
+ * contributions in ascending (s,k) order, grad_new_xyz[b,s] = - sum_k grad_out[(b,s,k), 0:3];
+ * rows whose index lies outside [0,N) contribute nothing. grad_xyz and grad_new_xyz go together
+ * (NULL: grad_out has D columns); grad_points is NULL exactly when D = 0. No atomics; a second
+ * run is bitwise identical. Limits as the forward's, and S * K < 2^31. */
+int ured_group_bwd(const float* grad_out, const int* idx, int B, int N, int S, int K, int D, float* grad_xyz,
+                   float* grad_new_xyz, float* grad_points, void* stream);
 
 /* ---------------- loss head (csrc/loss.hip) ---------------- */
 /* compute_cm_loss of the deformed shape `out` [B,S,3] and of its mirror image (x -> -x,
