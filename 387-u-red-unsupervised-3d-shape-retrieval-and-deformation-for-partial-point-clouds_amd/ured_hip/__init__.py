@@ -12,6 +12,7 @@
   ops      device-side part building (segment sums, AABBs)
   occ      partial (occluded) target clouds: ball / random / slice / part occlusion, centring, rotation
   group    PointNet++ set abstraction primitives: farthest-point sampling, ball query, grouping (GroupFn)
+  interp   PointNet++ feature propagation: three_nn and the inverse-distance interpolation (InterpFn)
   losshead the step's loss head (chamfer families, contrastive, residual, reconstruction, weighted sum)
 """
-from . import _lib, attn, group, kernels, losshead, nn, node, occ, ops, optim, syncbn  # noqa: F401
+from . import _lib, attn, group, interp, kernels, losshead, nn, node, occ, ops, optim, syncbn  # noqa: F401

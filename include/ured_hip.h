@@ -31,6 +31,9 @@
  *   ured_fps / ured_ball_query / ured_group_fwd / ured_group_bwd <- farthest_point_sample,
  *                       query_ball_point, index_points + sample_and_group and their autograd
  *                       (network/pointnet/pointnet2_utils.py:43-138).
+ *   ured_interp_fwd / ured_interp_bwd <- the three-neighbour inverse-distance interpolation and
+ *                       the cat of PointNetFeaturePropagation (pointnet2_utils.py:293-309) and
+ *                       their autograd.
  */
 #ifndef URED_HIP_H
 #define URED_HIP_H
@@ -43,7 +46,7 @@ extern "C" {
 #define URED_EINVAL 1001
 
 /* Library identification: returns URED_ABI_VERSION. */
-#define URED_ABI_VERSION 12  /* 12: ured_fps / ured_ball_query / ured_group_fwd / ured_group_bwd; 11: ured_knn_fwd / ured_knn_bwd; 10: ured_occlude; 9: ured_attn_fwd_sets / ured_attn_bwd_sets, ured_get_shape_src_fwd / _bwd; 8: ured_nn_bwd_set; 7: ured_copy_batch; 6: ured_part_rows_bwd_add; 5: node BN SyncBN fields (stats_out/stats_in, sums_out/sums_in); ured_bn_stats et al. */
+#define URED_ABI_VERSION 13  /* 13: ured_interp_fwd / ured_interp_bwd; 12: ured_fps / ured_ball_query / ured_group_fwd / ured_group_bwd; 11: ured_knn_fwd / ured_knn_bwd; 10: ured_occlude; 9: ured_attn_fwd_sets / ured_attn_bwd_sets, ured_get_shape_src_fwd / _bwd; 8: ured_nn_bwd_set; 7: ured_copy_batch; 6: ured_part_rows_bwd_add; 5: node BN SyncBN fields (stats_out/stats_in, sums_out/sums_in); ured_bn_stats et al. */
 int ured_abi_version(void);
 /* Thread-local message for the last failing call on this thread ("" if none). */
 const char* ured_last_error(void);
@@ -560,6 +563,30 @@ int ured_group_fwd(const float* xyz, const float* new_xyz, const float* points, 
  * run is bitwise identical. Limits as the forward's, and S * K < 2^31. */
 int ured_group_bwd(const float* grad_out, const int* idx, int B, int N, int S, int K, int D, float* grad_xyz,
                    float* grad_new_xyz, float* grad_points, void* stream);
+
+/* ---------------- feature propagation (csrc/interp.hip) ---------------- */
+/* Inverse-distance interpolation of coarse features over the K nearest coarse points, with the skip
+ * features in front (PointNetFeaturePropagation, pointnet2_utils.py:293-309). points2 [B,S,D2], idx
+ * int32 [B,N,K] (rows of points2, in [0,S)), d2 [B,N,K] (their squared distances), points1 [B,N,D1]
+ * (NULL with D1 = 0) -> out [B*N, D1 + D2] point-major: columns 0..D1-1 a copy of points1, then
+ *   r_k = 1.0f / (d_k + 1e-8f), R = (r_0 + r_1) + r_2, w_k = r_k / R,
+ *   out_c = ((w_0 * f_0c) + (w_1 * f_1c)) + w_2 * f_2c, f_k = points2[b, idx[b,n,k]]
+ * in fp32, IEEE divisions, no FMA contraction (K = 2: two terms; K = 1: w_0 = 1 and out = f_0 bit
+ * for bit). The weights go to w_out [B,N,K] for the backward. One launch.
+ * Limits: 1 <= K <= 3, N >= 1, S >= 1, D2 >= 1, B <= 65535, B * N * (D1 + D2) < 2^31,
+ * B * S * D2 < 2^31, N * K < 2^31. B = 0 is a no-op. */
+int ured_interp_fwd(const float* points2, const int* idx, const float* d2, const float* points1, int B, int N, int S,
+                    int K, int D1, int D2, float* out, float* w_out, void* stream);
+/* Its backward from grad_out [B*N, D1 + D2], WRITTEN (every element of both outputs is set):
+ *   grad_points2[b,s,c] = sum over the (n,k) with idx[b,n,k] = s of w[b,n,k] * grad_out[(b,n), D1 + c],
+ *     in fp32 from 0 in ascending (n,k) order (a product, then an add); no atomics, a second run is
+ *     bitwise identical;
+ *   grad_d2[b,n,k] = -((r_k * w_k) * sum_{j != k} w_j * (A_k - A_j)), A_k = sum_c grad_out_c * f_kc
+ *     (the gradient through the weights in the form that stays accurate where d_k = 0; K = 1: 0).
+ * The gradient of points1 is the first D1 columns of grad_out (the caller's view). Limits as the
+ * forward's. */
+int ured_interp_bwd(const float* grad_out, const float* points2, const int* idx, const float* w, const float* d2, int B,
+                    int N, int S, int K, int D1, int D2, float* grad_points2, float* grad_d2, void* stream);
 
 /* ---------------- loss head (csrc/loss.hip) ---------------- */
 /* compute_cm_loss of the deformed shape `out` [B,S,3] and of its mirror image (x -> -x,

@@ -5,11 +5,18 @@ against the torch composition a user had before them, on the same GPU in the sam
 
 Legs: farthest-point sampling 16x2048 -> 512 and 16x1024 -> 128; ball query 16x2048, S = 512,
 r = 0.2, nsample = 32; grouping forward + backward on that shape with D = 64; one set-abstraction
-layer (512, 0.2, 32, 3 + 3, [64, 64, 128]) forward + backward. The baselines: a Python loop of
+layer (512, 0.2, 32, 3 + 3, [64, 64, 128]) forward + backward; the feature-propagation interpolation
+(three neighbours given) forward + backward at 16x2048 from 512, D2 = 256; one feature-propagation
+layer (384, [256, 256]) forward + backward on that shape with D1 = 128; one multi-scale layer
+(512, [0.1, 0.2, 0.4], [32, 64, 128], 3, [[32, 32, 64], [64, 64, 128], [64, 96, 128]]) forward +
+backward. The baselines: a Python loop of
 npoint iterations (gather the centroid, distances, masked minimum update, argmax) for the sampling;
 the B x S x N distance matrix by |a|^2 + |b|^2 - 2ab, a mask and a sort for the ball query;
 advanced indexing and a cat (and their autograd) for the grouping; all of those plus
-Conv2d / BatchNorm2d / ReLU / max for the layer.
+Conv2d / BatchNorm2d / ReLU / max for the layer; for the interpolation the reciprocal weights,
+advanced indexing and weighted sum of the reference's feature propagation on the same neighbours,
+for its layer also the B x N x S distance matrix, the full sort, the cat and Conv1d / BatchNorm1d /
+ReLU; for the multi-scale layer the set-abstraction baseline once per scale and a cat.
 
 Each leg runs in a child process of its own under a time limit (a leg that fails or runs out of
 time ends the run; nothing further is started on the device); at most 16 CPU threads. Per leg both
@@ -26,7 +33,9 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LEGS = ["fps 16x2048->512", "fps 16x1024->128", "ball query 16x2048 S=512 r=0.2 ns=32",
-        "group fwd+bwd 16x2048 S=512 K=32 D=64", "SA layer fwd+bwd (512, 0.2, 32, 3+3, [64,64,128])"]
+        "group fwd+bwd 16x2048 S=512 K=32 D=64", "SA layer fwd+bwd (512, 0.2, 32, 3+3, [64,64,128])",
+        "interp fwd+bwd 16x2048 from 512 D2=256", "FP layer fwd+bwd (384, [256,256]) 16x2048 from 512",
+        "MSG layer fwd+bwd (512, [0.1,0.2,0.4], [32,64,128], 3, 3 scales)"]
 
 
 # ---------------- the torch baselines ----------------
@@ -76,6 +85,24 @@ def group_torch(xyz, new_xyz, points, idx):
     B, S, _ = new_xyz.shape
     g = gather_torch(xyz, idx) - new_xyz.view(B, S, 1, 3)
     return torch.cat([g, gather_torch(points, idx)], -1)
+
+
+def interp_torch(points2, idx, d):
+    """The reference's weights, gather and weighted sum (pointnet2_utils.py:300-303) on given neighbours."""
+    r = 1.0 / (d + 1e-8)
+    w = r / r.sum(dim=2, keepdim=True)
+    return (gather_torch(points2, idx) * w.unsqueeze(-1)).sum(dim=2)
+
+
+def three_nn_torch(xyz1, xyz2):
+    import torch
+    B, N, _ = xyz1.shape
+    S = xyz2.shape[1]
+    d = -2 * torch.matmul(xyz1, xyz2.transpose(1, 2))
+    d += (xyz1 ** 2).sum(-1).view(B, N, 1)
+    d += (xyz2 ** 2).sum(-1).view(B, 1, S)
+    d, idx = d.sort(dim=-1)
+    return d[:, :, :3], idx[:, :, :3]
 
 
 # ---------------- timing ----------------
@@ -156,6 +183,8 @@ def run_leg(leg, iters, rounds):
 
             fns = {"hip": lambda: step(lambda x, c, p: G.GroupFn.apply(x, c, p, idx)),
                    "torch": lambda: step(lambda x, c, p: group_torch(x, c, p, idl))}
+        elif i >= 5:
+            fns = _fp_msg_legs(i, torch, G, P, dev, g, xyz, new_xyz, start, res)
         else:
             layer = P.PointNetSetAbstraction(S, r, K, 3 + 3, [64, 64, 128], False).to(dev).train()
             feats = torch.randn(B, 3, N, generator=g).to(dev).requires_grad_(True)
@@ -181,6 +210,75 @@ def run_leg(leg, iters, rounds):
     res["torch_over_hip"] = res["torch"]["median_us"] / res["hip"]["median_us"]
     res["clock_mhz_after"] = _clock()
     return res
+
+
+def _fp_msg_legs(i, torch, G, P, dev, g, xyz, new_xyz, start, res):
+    """The feature-propagation and multi-scale legs: xyz [16,2048,3] fine, new_xyz [16,512,3] its sample."""
+    from ured_hip import interp as I
+    B, N, S = xyz.shape[0], xyz.shape[1], new_xyz.shape[1]
+    if i == 5:      # the interpolation alone, on given neighbours
+        D2 = 256
+        d, idx = I.three_nn(xyz, new_xyz)
+        idl = idx.long()
+        p2 = torch.randn(B, S, D2, generator=g).to(dev).requires_grad_(True)
+        dl = d.detach().clone().requires_grad_(True)
+        go = torch.randn(B * N, D2, generator=g).to(dev)
+        with torch.no_grad():
+            res["max_abs_diff"] = float((I.InterpFn.apply(None, p2, idx, dl).view(B, N, D2) - interp_torch(p2, idl, dl)).abs().max())
+
+        def step(fwd):
+            p2.grad = dl.grad = None
+            fwd().reshape(B * N, D2).backward(go)
+
+        return {"hip": lambda: step(lambda: I.InterpFn.apply(None, p2, idx, dl)),
+                "torch": lambda: step(lambda: interp_torch(p2, idl, dl))}
+    if i == 6:      # one feature-propagation layer, coordinates constant (as in a segmentation decoder's use)
+        D1, D2 = 128, 256
+        layer = P.PointNetFeaturePropagation(D1 + D2, [256, 256]).to(dev).train()
+        x1, x2 = xyz.transpose(1, 2).contiguous(), new_xyz.transpose(1, 2).contiguous()
+        p1 = torch.randn(B, D1, N, generator=g).to(dev).requires_grad_(True)
+        p2 = torch.randn(B, D2, S, generator=g).to(dev).requires_grad_(True)
+        go = torch.randn(B, 256, N, generator=g).to(dev)
+        leaves = list(layer.parameters()) + [p1, p2]
+
+        def torch_layer():
+            d, idx = three_nn_torch(xyz, new_xyz)
+            h = torch.cat([p1.permute(0, 2, 1), interp_torch(p2.permute(0, 2, 1), idx, d)], -1).permute(0, 2, 1)
+            for conv, bn in zip(layer.mlp_convs, layer.mlp_bns):
+                h = torch.relu(bn(conv(h)))
+            return h
+
+        def step(fwd):
+            for t in leaves:
+                t.grad = None
+            fwd().backward(go)
+
+        return {"hip": lambda: step(lambda: layer(x1, x2, p1, p2)), "torch": lambda: step(torch_layer)}
+    radii, ns, mlps = [0.1, 0.2, 0.4], [32, 64, 128], [[32, 32, 64], [64, 64, 128], [64, 96, 128]]
+    layer = P.PointNetSetAbstractionMsg(S, radii, ns, 3, mlps).to(dev).train()
+    feats = torch.randn(B, 3, N, generator=g).to(dev).requires_grad_(True)
+    x_bcn = xyz.transpose(1, 2).contiguous()
+    go = torch.randn(B, 64 + 128 + 128, S, generator=g).to(dev)
+    leaves = list(layer.parameters()) + [feats]
+
+    def torch_layer():
+        ft = feats.permute(0, 2, 1)
+        nx = gather_torch(xyz, fps_torch(xyz, S, start))
+        outs = []
+        for radius, k, convs, bns in zip(radii, ns, layer.conv_blocks, layer.bn_blocks):
+            idx = ball_torch(radius, k, xyz, nx)
+            h = torch.cat([gather_torch(ft, idx), gather_torch(xyz, idx) - nx.view(B, S, 1, 3)], -1).permute(0, 3, 2, 1)
+            for conv, bn in zip(convs, bns):
+                h = torch.relu(bn(conv(h)))
+            outs.append(h.max(2)[0])
+        return torch.cat(outs, 1)
+
+    def step(fwd):
+        for t in leaves:
+            t.grad = None
+        fwd().backward(go)
+
+    return {"hip": lambda: step(lambda: layer(x_bcn, feats, start=start)[1]), "torch": lambda: step(torch_layer)}
 
 
 def main():
