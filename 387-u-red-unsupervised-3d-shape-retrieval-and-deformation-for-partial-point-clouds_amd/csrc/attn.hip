@@ -14,6 +14,7 @@
 // consecutive key rows) are bank-conflict free. fp32 throughout, fixed summation order
 // (deterministic).
 #define URED_DBG_FILE 6
+#include <atomic>
 #include "ured_common.h"
 #include "ured_hip.h"
 
@@ -188,12 +189,24 @@ int check_sizes(const char* who, int B, int H, int n, int m, int d) {
 size_t fwd_lds(int n, int m, int d) { return sizeof(float) * ((size_t)(n + 2 * m) * (d + 1) + (size_t)n * m); }
 size_t bwd_lds(int n, int m, int d) { return sizeof(float) * ((size_t)(2 * n + 2 * m) * (d + 1) + 2 * (size_t)n * m); }
 
+// A launch may ask for 64 KB of dynamic LDS by default. The forward stays below it at the declared
+// maxima (53,632 B at n = m = 32, d = 128); the backward's image there is 74,240 B (from n = m = 29
+// at d = 128), of the 160 KiB a gfx950 workgroup can hold, so the backward kernel's limit is raised
+// to that worst case, once per device, before the first launch that needs more than the default.
+constexpr size_t LDS_DEFAULT = 65536;
+constexpr size_t BWD_LDS_MAX =
+    sizeof(float) * ((size_t)(4 * URED_ATTN_MAX_NODES) * (URED_ATTN_MAX_HEAD_DIM + 1) +
+                     2 * (size_t)URED_ATTN_MAX_NODES * URED_ATTN_MAX_NODES);
+
 
 // Validate one set and add it to the launch table (B == 0 sets add no workgroups).
 int add_set(const char* who, bool bwd, const UredAttnSet& x, AttnSets& S, size_t& lds) {
     if (int rc = check_sizes(who, x.B, x.H, x.n, x.m, x.d)) return rc;
+    // every admitted shape fits: the forward within the default 64 KB of dynamic LDS, the backward
+    // within BWD_LDS_MAX (launch_sets raises the kernel's limit for a launch above 64 KB)
     const size_t need = bwd ? bwd_lds(x.n, x.m, x.d) : fwd_lds(x.n, x.m, x.d);
-    URED_REQUIRE(need <= 65536, "%s: n=%d m=%d d=%d needs more than 64 KB of LDS", who, x.n, x.m, x.d);
+    const size_t limit = bwd ? BWD_LDS_MAX : LDS_DEFAULT;
+    URED_REQUIRE(need <= limit, "%s: n=%d m=%d d=%d needs %zu B of LDS (limit %zu)", who, x.n, x.m, x.d, need, limit);
     if (x.B == 0) return 0;
     const int hd = x.H * x.d;
     URED_REQUIRE(x.q && x.k && x.v && x.weights, "%s: null pointer", who);
@@ -226,6 +239,19 @@ int launch_sets(const char* who, bool bwd, int nsets, const UredAttnSet* sets, v
         if (int rc = add_set(who, bwd, sets[i], S, lds)) return rc;
     const int blocks = S.first[S.nsets];
     if (blocks == 0) return 0;
+    if (lds > LDS_DEFAULT) {                   // backward only (add_set holds the forward to the default)
+        static std::atomic<bool> raised[64];   // per device; the call is idempotent, so a race only repeats it
+        int devi = 0;
+        hipError_t e = hipGetDevice(&devi);
+        if (e == hipSuccess && (devi < 0 || devi >= 64 || !raised[devi].load())) {
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)BWD_LDS_MAX);
+            if (e == hipSuccess && devi >= 0 && devi < 64) raised[devi].store(true);
+        }
+        if (e != hipSuccess)
+            return ured::set_error((int)e, "%s: cannot raise the dynamic LDS limit to %zu B: %s", who, BWD_LDS_MAX,
+                                   hipGetErrorString(e));
+    }
     if (bwd) hipLaunchKernelGGL(attn_bwd_kernel, dim3(blocks), dim3(ATT_THREADS), lds, (hipStream_t)stream, S);
     else hipLaunchKernelGGL(attn_fwd_kernel, dim3(blocks), dim3(ATT_THREADS), lds, (hipStream_t)stream, S);
     return ured::launch_status(who);

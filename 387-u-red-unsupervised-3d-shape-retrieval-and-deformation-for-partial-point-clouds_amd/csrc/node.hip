@@ -618,7 +618,8 @@ extern "C" {
 static int check_node_job(const UredNodeGemmDesc& d, NodeJob& J) {
     URED_REQUIRE(d.M >= 0 && d.N >= 0 && d.K >= 0, "ured_node_gemm: bad sizes %d x %d x %d", d.M, d.N, d.K);
     if (d.kind == URED_NODE_COLSUM) {
-        URED_REQUIRE(d.A && d.C, "ured_node_gemm: colsum job needs A and C");
+        // an empty tensor's address may be null: no row of it is read
+        URED_REQUIRE((d.A || d.M == 0) && d.C, "ured_node_gemm: colsum job needs A and C");
         J.d = d;
         J.akc = J.bkc = 0;
         J.ntn = (d.N + 31) / 32;
@@ -663,7 +664,9 @@ int ured_node_gemm_batch(const UredNodeGemmDesc* const* ds, int n, void* stream)
     for (int i = 0; i < n; ++i) {
         URED_REQUIRE(ds[i], "ured_node_gemm_batch: null descriptor");
         const UredNodeGemmDesc& d = *ds[i];
-        if (d.M == 0 || d.N == 0) continue;
+        // nothing to write: no columns, or a GEMM without rows. A column sum over zero rows still
+        // owns its N outputs (zeros, or C unchanged when it accumulates): node_colsum handles M == 0
+        if (d.N == 0 || (d.M == 0 && d.kind != URED_NODE_COLSUM)) continue;
         NodeJob& J = jobs.job[jobs.njobs];
         const int rc = check_node_job(d, J);
         if (rc) return rc;

@@ -128,7 +128,14 @@ def colsum_desc(g, out, accumulate=False):
 
 
 def launch(*descs):
-    """Run independent node GEMMs (up to 4 per launch) on the current stream."""
+    """Run independent node jobs (GEMMs and column sums) on the current stream, up to MAX_JOBS
+    (6, the library's URED_NODE_MAX_JOBS) per launch; more are split over several launches. No
+    order holds between the jobs of one launch. A launch runs on the v4 kernel when every GEMM in it
+    has K, k1 and n1 multiples of 32, else on v1 (bitwise the same results). A job with N = 0, and a
+    GEMM with M = 0, writes nothing; a GEMM with K = 0 writes its epilogue; a column sum over M = 0
+    rows writes zeros (or leaves C as it is when it accumulates). tests/test_node_kernels_gpu.py
+    holds each of these, every operand layout and epilogue option and the v1 / v4 agreement to the
+    float64 restatement tests/node_ref.py."""
     stream = _lib.current_stream()
     for i in range(0, len(descs), MAX_JOBS):
         part = descs[i:i + MAX_JOBS]

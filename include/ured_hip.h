@@ -376,7 +376,9 @@ int ured_group_colsum_split(const float* X, int ldx, int N, const int* off, int 
  *   weights[b][h][i][j] = softmax_j(scale * <q_bi^h, k_bj^h>),  out_bi^h = sum_j weights * v_bj^h
  * weights [B*H*n*m] is written by the forward and read by the backward, which overwrites
  * dq [B,n,*], dk/dv [B,m,*] (may be column slices of one buffer). Limits: n, m <= 32,
- * d <= 128, and the (n, m, d) LDS image within 64 KB. */
+ * d <= 128; every such shape runs forward and backward (the backward's LDS image reaches
+ * 74,240 B at the maxima, above the 64 KB a launch may ask for by default: the library raises
+ * the backward kernel's limit before the first launch that needs it). */
 #define URED_ATTN_MAX_NODES 32
 #define URED_ATTN_MAX_HEAD_DIM 128
 int ured_attn_fwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
