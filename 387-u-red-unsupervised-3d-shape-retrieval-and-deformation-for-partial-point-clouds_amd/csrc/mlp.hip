@@ -6,19 +6,36 @@
 //
 // Activations are point-major [M][C] (C contiguous), so a 1x1 conv is the GEMM
 // Y = X W^T with M = points (up to 262,144 here), N = Cout, K = Cin. The GEMM
-// runs on v_mfma_f32_32x32x2_f32 (fp32 in, fp32 accumulate, exact fma chains).
+// runs on v_mfma_f32_32x32x2_f32 (fp32 in, fp32 accumulate, exact fma chains), in one of two
+// kernels with the same block tile, accumulator layout, epilogues and results:
 //
+//  * gemm2_kernel (v2), the kernel of the step's shapes: both operands reach LDS by
+//    buffer-descriptor DMA (no staging registers), two LDS stages with the next K-step's DMA in
+//    flight under the current step's MFMAs, the previous layer's BN+ReLU applied to the fragments
+//    after the LDS read, buffer stores in the epilogue; 64-row / 64-column tile variants for the
+//    narrow layers. Details over the kernel.
+//  * gemm_kernel (v1), the fallback: the next K-tile is prefetched into registers while the
+//    current one is consumed (T14 split: issue early, write LDS after the barrier) and written
+//    to LDS reduction-major (As[k][m], Bs[k][n]; row-major global operands transposed on the
+//    write with row pad 1, k-major ones copied with pad 4), the prologue applied at that write;
+//    float4 (VEC) or scalar loads.
+//
+// launch() takes v2 unless one of these holds, and then v1:
+//  * vec_ok fails (v1 with scalar loads): A, B, A2 or the prologue vectors not 16-B aligned, lda
+//    or ldb not a multiple of 4, or a contiguous extent not a multiple of 4 (row-major A: K, k1,
+//    and lda2 of a concatenated A2; k-major A: M; row-major B: K; k-major B: N);
+//  * v2_ok fails: an A prologue over k1 channels with k1 % 16 != 0, or on a row-major A with
+//    k1 > 1024 (PRO_LDS); K < 4; a k-major A with M < 4 or a k-major B with N < 4;
+//  * buf_ok fails: A, B, C or Yp spans 2 GiB or more (32-bit buffer offsets), or a concatenated
+//    A2 that is k-major, null, 2 GiB or more, or starts off a K-step (k1 % 32 != 0).
+// Before either, launch() sends the forward and dgrad edge layers with K <= 4 to the streaming
+// kernels (fwd_small_ok, dgrad_small_ok).
+//
+// Common to both kernels:
 //  * block tile 128x128, BK = 32, 256 threads = 2x2 waves, each wave 64x64 =
 //    2x2 MFMA 32x32 tiles (64 accumulator registers);
-//  * LDS holds both operands reduction-major (As[k][m], Bs[k][n]) so every
-//    MFMA operand is one conflict-free ds_read_b32 per lane; row-major global
-//    operands are transposed on the LDS write (row pad 1 -> conflict-free
-//    ds_write_b32), k-major ones are copied (pad 4 -> ds_write_b128);
-//  * the next K-tile is prefetched into registers while the current one is
-//    consumed (T14 split: issue early, write LDS after the barrier);
-//  * fused prologue: the previous layer's BatchNorm + ReLU is applied while
-//    staging the operand (relu(x*s+t) or relu(x)*s+t), so normalised
-//    activations are never written to HBM;
+//  * fused prologue: the previous layer's BatchNorm + ReLU (relu(x*s+t) or relu(x)*s+t) is
+//    applied on the way to the MFMA, so normalised activations are never written to HBM;
 //  * fused epilogues: bias / per-group row bias, BN batch-statistics partials
 //    (per-block mean & M2, merged in fp64 by ured_bn_fwd_finalize — Chan's
 //    parallel variance, order-fixed, deterministic), max-pool partials, the
@@ -236,7 +253,6 @@ __device__ __forceinline__ bool ts_shape(const UredGemmDesc& d) {
 // element (i, j, r): row = m0 + wm*64 + i*32 + (r&3) + 8*(r>>2) + 4*(lane>>5), col = n0 + wn*64 + j*32 + (lane&31)
 #define RED(a, q, c) red_f[((a) * 2 + (q)) * BN + (c)]
 #define REDI(a, q, c) red_i[((a) * 2 + (q)) * BN + (c)]
-struct NoPre { __device__ void operator()() const {} };
 
 // Workgroup barrier that orders LDS only. __syncthreads() also carries a release fence for
 // global memory, i.e. a vmcnt(0) that waits for every outstanding store of the wave; the
@@ -247,22 +263,20 @@ __device__ __forceinline__ void lds_barrier() {
 }
 
 // Output writer. BUF (v2 kernel): every lane issues every store as a buffer store and an
-// out-of-range element gets an offset past num_records (the hardware drops it), so a wave
-// always issues exactly 64 stores per output tile, unconditionally: the persistent kernel
-// relies on that count to wait for its prefetch DMA without waiting for the stores.
-constexpr unsigned ST_OOB = 0x80000000u;
+// out-of-range element gets an offset past num_records (the hardware drops it): a select per
+// element instead of a branch around each store.
 template <bool BUF>
 struct OutTile {
     float* base; int ld;
-    unsigned ld4;        // row pitch in bytes, laundered per tile (see below)
+    unsigned ld4;        // row pitch in bytes, opaque to the optimiser (see below)
     unsigned nrec;       // num_records of the descriptor (bytes)
     __amdgpu_buffer_rsrc_t rsrc;
     __device__ OutTile(float* b, int ld_, int M, int N) : base(b), ld(ld_) {
         if constexpr (BUF) {
             nrec = (unsigned)(((long long)(M - 1) * ld_ + N) * 4);
-            rsrc = __builtin_amdgcn_make_buffer_rsrc(b, (short)0, (int)nrec, 0x00020000);
-            // opaque to the optimiser: keeps the 64 per-element row products from being
-            // hoisted out of the persistent tile loop (and spilled)
+            rsrc = __builtin_amdgcn_make_buffer_rsrc(b, (short)0, (int)nrec, BUF_DWORD3);
+            // Opaque to the optimiser. Kept because removing it changes the generated code (44
+            // of the file's kernels); the alternative was not measured.
             ld4 = (unsigned)ld_ * 4u;
             asm volatile("" : "+s"(ld4));
         }
@@ -274,17 +288,13 @@ struct OutTile {
 #if URED_DEBUG_BOUNDS
             URED_DBG_CHECK(!(ok && (row < 0 || col < 0 || off + 4u > nrec)));
 #endif
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrc, ok ? off : ST_OOB, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrc, ok ? off : BUF_OOB, 0, 0);
         } else if (ok) {
             base[(size_t)row * ld + col] = v;
         }
     }
 };
 
-// `pre` runs once all of the epilogue's own global loads are issued and before any of them
-// is consumed: the persistent kernel issues the next tile's first LDS-DMA there, so it lands
-// while this epilogue computes and stores (vmcnt counts in order, so a DMA issued earlier
-// would make every epilogue load wait for it).
 // Matching reader (BN-backward Yp). BUF: buffer loads at 32-bit offsets; rows/columns
 // outside [M, N) read as 0 (their results are never stored). Otherwise clamped loads.
 template <bool BUF>
@@ -295,7 +305,9 @@ struct InTile {
     __device__ InTile(const float* b, int ld_, int M_, int N_) : base(b), ld(ld_), M(M_), N(N_) {
         if constexpr (BUF) {
             rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(b), (short)0,
-                                                     (int)(((long long)(M_ - 1) * ld_ + N_) * 4), 0x00020000);
+                                                     (int)(((long long)(M_ - 1) * ld_ + N_) * 4), BUF_DWORD3);
+            // opaque like OutTile's: kept because removing it changes the generated code (the
+            // two v2 BN-backward dgrad kernels); the alternative was not measured
             ld4 = (unsigned)ld_ * 4u;
             asm volatile("" : "+s"(ld4));
         }
@@ -303,7 +315,7 @@ struct InTile {
     __device__ __forceinline__ float get(int row, int col) const {
         if constexpr (BUF) {
             const unsigned off = (unsigned)row * ld4 + (unsigned)col * 4u;
-            return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, col < N ? off : ST_OOB, 0, 0));
+            return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, col < N ? off : BUF_OOB, 0, 0));
         } else {
             row = row < M ? row : M - 1;
             col = col < N ? col : N - 1;
@@ -317,18 +329,20 @@ struct InTile {
 // without its per-element bounds selects, and with the Yp loads / G stores addressed as a per-lane
 // buffer offset plus a scalar row offset (no per-element 32-bit multiplies). Same operations in the
 // same order as the general loop, so the results are bitwise the same.
-template <int ACT, bool POOL, int TN, class Pre>
+template <int ACT, bool POOL, int TN>
 __device__ __forceinline__ void bnbwd_full(const UredGemmDesc& d, f16v (&acc)[2][2], int m0, int n0, float (&s1)[2],
-                                           float (&s2)[2], Pre pre) {
+                                           float (&s2)[2]) {
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, wm = w & 1, wn = w >> 1;
     const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(d.Yp), (short)0,
-                                                                         (int)(((long long)(d.M - 1) * d.ldy + d.N) * 4), 0x00020000);
+                                                                         (int)(((long long)(d.M - 1) * d.ldy + d.N) * 4), BUF_DWORD3);
     const __amdgpu_buffer_rsrc_t cr = __builtin_amdgcn_make_buffer_rsrc(d.C, (short)0,
-                                                                         (int)(((long long)(d.M - 1) * d.ldc + d.N) * 4), 0x00020000);
+                                                                         (int)(((long long)(d.M - 1) * d.ldc + d.N) * 4), BUF_DWORD3);
     const unsigned ly = (unsigned)d.ldy * 4u, lc = (unsigned)d.ldc * 4u;
     const unsigned r0 = (unsigned)(m0 + wm * 64 + 4 * (lane >> 5));       // this lane's first row
+    auto col_of = [&](int j) { return n0 + wn * (32 * TN) + j * 32 + (lane & 31); };
     // rows of element (i, r): r0 + i*32 + (r&3) + 8*(r>>2) -> scalar offset (i*32 + (r&3) + 8*(r>>2)) * ld,
     // from an opaque copy of ld so that the products are s_muls at their use, not hoisted SGPRs
+    // (kept: removing it changes the generated code of the dgrad kernels; the alternative was not measured)
     auto roff = [&](int i, int r, unsigned ld) {
         asm volatile("" : "+s"(ld));
         return (unsigned)(i * 32 + (r & 3) + 8 * (r >> 2)) * ld;
@@ -336,7 +350,7 @@ __device__ __forceinline__ void bnbwd_full(const UredGemmDesc& d, f16v (&acc)[2]
     float yh[2][2][16];
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
-        const unsigned vo = r0 * ly + (unsigned)(n0 + wn * (32 * TN) + j * 32 + (lane & 31)) * 4u;
+        const unsigned vo = r0 * ly + (unsigned)col_of(j) * 4u;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -348,19 +362,18 @@ __device__ __forceinline__ void bnbwd_full(const UredGemmDesc& d, f16v (&acc)[2]
     const int pg = POOL ? m0 / d.pool_group_rows : 0;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
-        const int col = n0 + wn * (32 * TN) + j * 32 + (lane & 31);
+        const int col = col_of(j);
         sc_[j] = d.bn_scale[col]; sh_[j] = d.bn_shift[col]; mu_[j] = d.bn_mean[col]; is_[j] = d.bn_invstd[col];
         pidx_[j] = -1; pgr_[j] = 0.f;
         if (POOL) { pidx_[j] = d.pool_idx[(size_t)pg * d.N + col]; pgr_[j] = d.pool_grad[(size_t)pg * d.N + col]; }
     }
-    pre();
 #if URED_GEMM_TIMING
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     URED_TS_MARK(d, 8);
 #endif
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
-        const unsigned vo = r0 * lc + (unsigned)(n0 + wn * (32 * TN) + j * 32 + (lane & 31)) * 4u;
+        const unsigned vo = r0 * lc + (unsigned)col_of(j) * 4u;
         const int prow = pidx_[j] - (int)r0;       // the pooled winner's row relative to this lane's first row
         float a1 = 0.f, a2 = 0.f;
 #pragma unroll
@@ -396,26 +409,26 @@ __device__ __forceinline__ void bnbwd_full(const UredGemmDesc& d, f16v (&acc)[2]
     URED_TS_MARK(d, 9);
 }
 
-template <int EPI, bool BUFST = false, int TM = 2, int TN = 2, class Pre = NoPre>
+template <int EPI, bool BUFST = false, int TM = 2, int TN = 2>
 __device__ __forceinline__ void epilogue(const UredGemmDesc& d, f16v (&acc)[2][2], int m0, int n0,
-                                         float* red_f, int* red_i, Pre pre = Pre()) {
+                                         float* red_f, int* red_i) {
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, wm = w & 1, wn = w >> 1;
     // element (i, j, r): row = m0 + wm*64 + i*32 + (r&3) + 8*(r>>2) + 4*(lane>>5), col = n0 + wn*64 + j*32 + (lane&31)
     const int rbase = m0 + wm * (32 * TM) + 4 * (lane >> 5);
     auto row_of = [&](int i, int r) { return rbase + i * 32 + (r & 3) + 8 * (r >> 2); };
+    auto col_of = [&](int j) { return n0 + wn * (32 * TN) + j * 32 + (lane & 31); };
 
     if (EPI == URED_EPI_STORE || EPI == URED_EPI_SPLITK) {
         OutTile<BUFST> C(d.C + (EPI == URED_EPI_SPLITK ? (size_t)blockIdx.z * d.M * d.ldc : 0), d.ldc, d.M, d.N);
         float bsv[2];
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-            const int col = n0 + wn * (32 * TN) + j * 32 + (lane & 31);
+            const int col = col_of(j);
             bsv[j] = (EPI == URED_EPI_STORE && d.bias && col < d.N) ? d.bias[col] : 0.f;
         }
-        pre();
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-            const int col = n0 + wn * (32 * TN) + j * 32 + (lane & 31);
+            const int col = col_of(j);
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -439,15 +452,14 @@ __device__ __forceinline__ void epilogue(const UredGemmDesc& d, f16v (&acc)[2][2
         float bsv_[2];
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-            const int col = n0 + wn * (32 * TN) + j * 32 + (lane & 31);
+            const int col = col_of(j);
             const bool cv = col < d.N;
             bsv_[j] = (cv && d.bias) ? d.bias[col] : 0.f;
             if (rb_blk && cv) bsv_[j] += d.rowbias[(size_t)(m0 / d.group_rows) * d.ldr + col];
         }
-        pre();
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-            const int col = n0 + wn * (32 * TN) + j * 32 + (lane & 31);
+            const int col = col_of(j);
             const bool cv = col < d.N;
             const float bsv = bsv_[j];
             if (!d.rowbias || rb_blk) {   // common case: no per-element branch or load
@@ -593,23 +605,23 @@ __device__ __forceinline__ void epilogue(const UredGemmDesc& d, f16v (&acc)[2][2
         const bool full = BUFST && m0 + 64 * TM <= d.M && n0 + 64 * TN <= d.N && !d.gadd && (!d.pool_idx || pool_al);
         if (full) {
             if (pool_al) {
-                if (d.bwd_res == URED_ACT_RES) bnbwd_full<URED_ACT_RES, true, TN>(d, acc, m0, n0, s1, s2, pre);
-                else if (d.bwd_res == URED_ACT_BN) bnbwd_full<URED_ACT_BN, true, TN>(d, acc, m0, n0, s1, s2, pre);
-                else bnbwd_full<URED_ACT_ENC, true, TN>(d, acc, m0, n0, s1, s2, pre);
+                if (d.bwd_res == URED_ACT_RES) bnbwd_full<URED_ACT_RES, true, TN>(d, acc, m0, n0, s1, s2);
+                else if (d.bwd_res == URED_ACT_BN) bnbwd_full<URED_ACT_BN, true, TN>(d, acc, m0, n0, s1, s2);
+                else bnbwd_full<URED_ACT_ENC, true, TN>(d, acc, m0, n0, s1, s2);
             } else {
-                if (d.bwd_res == URED_ACT_RES) bnbwd_full<URED_ACT_RES, false, TN>(d, acc, m0, n0, s1, s2, pre);
-                else if (d.bwd_res == URED_ACT_BN) bnbwd_full<URED_ACT_BN, false, TN>(d, acc, m0, n0, s1, s2, pre);
-                else bnbwd_full<URED_ACT_ENC, false, TN>(d, acc, m0, n0, s1, s2, pre);
+                if (d.bwd_res == URED_ACT_RES) bnbwd_full<URED_ACT_RES, false, TN>(d, acc, m0, n0, s1, s2);
+                else if (d.bwd_res == URED_ACT_BN) bnbwd_full<URED_ACT_BN, false, TN>(d, acc, m0, n0, s1, s2);
+                else bnbwd_full<URED_ACT_ENC, false, TN>(d, acc, m0, n0, s1, s2);
             }
         } else {
-        // Yp is loaded whole (both column halves, 64 values) before pre(), the persistent kernel's
-        // next-tile DMA: after the K-loop the fragment registers are dead, so the tile fits under
-        // the kernel's VGPR peak, and the epilogue waits for one HBM round trip instead of two
-        // (gfx9 vmcnt is in order: a second half's loads would queue behind the first half's stores)
+        // Yp is loaded whole (both column halves, 64 values) before anything is stored: after the
+        // K-loop the fragment registers are dead, so the tile fits under the kernel's VGPR peak,
+        // and the epilogue waits for one HBM round trip instead of two (gfx9 vmcnt is in order: a
+        // second half's loads would queue behind the first half's stores)
         f16v yh[2][2];
         InTile<BUFST> Yr(d.Yp, d.ldy, d.M, d.N);
         auto load_y = [&](int j) {
-            const int col = n0 + wn * (32 * TN) + j * 32 + (lane & 31);
+            const int col = col_of(j);
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -622,7 +634,7 @@ __device__ __forceinline__ void epilogue(const UredGemmDesc& d, f16v (&acc)[2][2
         int pidx_[2];
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-            const int col = n0 + wn * (32 * TN) + j * 32 + (lane & 31);
+            const int col = col_of(j);
             const bool cv = col < d.N;
             const int cc = cv ? col : 0;
             sc_[j] = d.bn_scale[cc]; sh_[j] = d.bn_shift[cc]; mu_[j] = d.bn_mean[cc]; is_[j] = d.bn_invstd[cc];
@@ -630,7 +642,6 @@ __device__ __forceinline__ void epilogue(const UredGemmDesc& d, f16v (&acc)[2][2
             if (pool_blk && cv) { pidx_[j] = d.pool_idx[(size_t)pg * d.N + col]; pgr_[j] = d.pool_grad[(size_t)pg * d.N + col]; }
         }
         load_y(0); load_y(1);   // behind the (L2-resident) per-column parameters
-        pre();
         OutTile<BUFST> Gw(d.C, d.ldc, d.M, d.N);
         // per-element global reads (a residual gradient, or pooled gradients of groups that do
         // not align with the 128-row block) take the general loop below
@@ -639,6 +650,8 @@ __device__ __forceinline__ void epilogue(const UredGemmDesc& d, f16v (&acc)[2][2
         const float ylo = d.bwd_res == URED_ACT_RES ? 0.f : -__builtin_inff();
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
+            // col_of(j) spelled out: through the lambda here, the dgrad kernels get another
+            // register allocation (two more SGPR spills in v1)
             const int col = n0 + wn * (32 * TN) + j * 32 + (lane & 31);
             const bool cv = col < d.N;
             const float sc = sc_[j], sh = sh_[j], mu = mu_[j], is = is_[j];
@@ -728,7 +741,7 @@ __device__ __forceinline__ void epilogue(const UredGemmDesc& d, f16v (&acc)[2][2
 #undef RED
 #undef REDI
 
-// ---- the kernel ---------------------------------------------------------------
+// ---- v1: register-staged kernel (the fallback, any shape) -----------------------
 // Double-buffered LDS: tile t+1 is loaded to registers before the MFMAs of tile t and
 // written to the other buffer after them; one barrier per K-tile.
 template <bool A_KM, bool B_KM, int PRO_A, int PRO_B, int EPI, bool VEC>
@@ -804,7 +817,7 @@ __global__ __launch_bounds__(NT, 2) void gemm_kernel(const UredGemmDesc d) {
 }
 
 
-// ---- v2: LDS-DMA staged, persistent kernel (all-VEC shapes) ---------------------
+// ---- v2: LDS-DMA staged kernel (all-VEC shapes) -----------------------------------
 // Both operands reach LDS by buffer_load_dwordx4 ... lds (no VGPR round trip, no staging
 // registers): a row-major [rows][k] operand lands as a [128][32] image with its 16-B
 // slots XOR-swizzled by ((row >> 1) & 7) and is read 4 consecutive k per ds_read_b128 (that
@@ -823,12 +836,10 @@ typedef __attribute__((address_space(3))) void lds_void_t;
 // buffer-descriptor DMAs (operands < 2 GiB). Row-major: chunk c = (row r = c>>3, slot
 // p = c&7) reads k = 4*(p ^ ((r>>1)&7)) (the XOR swizzle is on the source address, the LDS image
 // stays lane-linear); k-major: chunk c = (k = c>>5, 4 columns at 4*(c&31)). The per-lane
-// byte offsets are computed once per tile; a K-step only adds its k offset. Lanes whose row (row-major) or
+// byte offsets are computed once per block; a K-step only adds its k offset. Lanes whose row (row-major) or
 // column (k-major) is outside the operand get an offset past num_records, and so does any
 // k >= K row of a k-major operand: the hardware returns zeros for them.
-constexpr unsigned BUF_OOB = 0x80000000u;
 constexpr int PRO_LDS = 1024;            // max prologue channels staged in LDS by gemm2
-constexpr int BUF_DWORD3 = 0x00020000;   // raw buffer, gfx9 family (gfx950)
 
 __host__ __device__ inline bool buf_ok(const UredGemmDesc& d) {
     // a concatenated second A source must start on a K-step boundary (one descriptor per step)
@@ -892,13 +903,6 @@ __device__ __forceinline__ void buf_tile(const BufOperand& o, int ld, int k0, fl
         __builtin_amdgcn_raw_ptr_buffer_load_lds(o.rs, (lds_void_t*)(base + i * 1024), 16, o.vo[i] + toff, 0, 0, 0);
 }
 
-template <int PRO>
-__device__ __forceinline__ float pro_v(float x, float s, float t) {
-    if (PRO == URED_PRO_ENC) return fmaxf(__builtin_fmaf(x, s, t), 0.f);
-    if (PRO == URED_PRO_RES) return __builtin_fmaf(fmaxf(x, 0.f), s, t);
-    return x;
-}
-
 // TM / TN: 32-row / 32-column MFMA tiles per wave (2 x 2 waves per block), so the block tile is
 // (64 TM) x (64 TN): 128 x 128 for the wide layers; TN = 1 (128 x 64) for outputs of <= 64
 // columns and TM = 1 (64 x ...) for split-K / store GEMMs of <= 64 output rows — the 32- and
@@ -935,8 +939,7 @@ __global__ __launch_bounds__(NT, 2) void gemm2_kernel(const UredGemmDesc d) {
     // one output tile per block: tile blockIdx.x -> xcd_remap (blocks sharing an A panel on one XCD)
     if ((int)blockIdx.x >= ntiles) return;
 #if URED_GEMM_TIMING
-    const bool ts_on = EPI == URED_EPI_BNBWD && d.M == URED_TS_M && d.N == URED_TS_N && d.K == URED_TS_K &&
-                       blockIdx.x < TS_SLOTS;
+    const bool ts_on = EPI == URED_EPI_BNBWD && ts_shape(d);
     unsigned long long ts_[4];
     ts_[0] = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -1082,14 +1085,14 @@ __global__ __launch_bounds__(NT, 2) void gemm2_kernel(const UredGemmDesc d) {
 #pragma unroll
                 for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
-                    for (int j = 0; j < 16; ++j) a[tm][j] = pro_v<PRO_A>(a[tm][j], ss[j], tt[j]);
+                    for (int j = 0; j < 16; ++j) a[tm][j] = pro_apply(PRO_A, a[tm][j], ss[j], tt[j]);
             }
         }
         if constexpr (B_KM && PRO_B != URED_PRO_NONE) {
 #pragma unroll
             for (int tn = 0; tn < TN; ++tn)
 #pragma unroll
-                for (int j = 0; j < 16; ++j) b[tn][j] = pro_v<PRO_B>(b[tn][j], bs_[tn], bt_[tn]);
+                for (int j = 0; j < 16; ++j) b[tn][j] = pro_apply(PRO_B, b[tn][j], bs_[tn], bt_[tn]);
         }
         if (tail) {   // zero the k >= K part of the reduction (the images hold clamped copies)
 #pragma unroll
@@ -1219,10 +1222,10 @@ __global__ __launch_bounds__(256) void wgrad_skinny_kernel(const float* __restri
     auto accum = [&](float (&big)[VEC], float (&small)[S]) {
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
-            const float bv = SMALL_IS_OUT ? pro_v<PRO>(big[v], bs[v], bt[v]) : big[v];
+            const float bv = SMALL_IS_OUT ? pro_apply(PRO, big[v], bs[v], bt[v]) : big[v];
 #pragma unroll
             for (int q = 0; q < S; ++q) {
-                const float sv = SMALL_IS_OUT ? small[q] : pro_v<PRO>(small[q], ss[q], st[q]);
+                const float sv = SMALL_IS_OUT ? small[q] : pro_apply(PRO, small[q], ss[q], st[q]);
                 acc[v][q] = __builtin_fmaf(sv, bv, acc[v][q]);
             }
         }

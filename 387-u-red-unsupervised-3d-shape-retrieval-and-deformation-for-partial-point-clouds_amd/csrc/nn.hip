@@ -34,9 +34,6 @@ constexpr int NN_THREADS = 256;
 constexpr int NN_TILE = 1024;   // refs per LDS tile (12 KiB SoA)
 constexpr int NN_CHUNK = 16;    // refs per min-tracking chunk
 constexpr float NN_PAD = 1.0e30f;  // padding coordinate: distance overflows to +inf
-#ifndef URED_NN_TILE_ALL
-#define URED_NN_TILE_ALL 1
-#endif
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 
@@ -319,7 +316,7 @@ template <int QPT, int RS>
 void launch_fwd(const NNFwdArgs& a, int max_q, int max_r, int nseg, int ndirs, hipStream_t st) {
     constexpr int QB = (NN_THREADS / RS) * QPT;
     dim3 grid((max_q + QB - 1) / QB, nseg, ndirs);
-    if (URED_NN_TILE_ALL && max_r <= NN_TILE_ALL)
+    if (max_r <= NN_TILE_ALL)
         hipLaunchKernelGGL((nn_fwd_kernel<QPT, RS, NN_TILE_ALL>), grid, dim3(NN_THREADS), 0, st, a);
     else
         hipLaunchKernelGGL((nn_fwd_kernel<QPT, RS>), grid, dim3(NN_THREADS), 0, st, a);
@@ -342,7 +339,7 @@ int fwd_dispatch(const NNFwdArgs& a, int nseg, int max_a, int max_b, hipStream_t
     // With the whole-set tile the split is at least 4 ref groups: a ragged launch (the loss head's
     // part family: 512 segments, a quarter of them non-empty) is sized by its bounds, so waves1
     // overstates its work; 4 groups cost one small LDS combine where the bound is tight.
-    const bool all = URED_NN_TILE_ALL && max_r <= NN_TILE_ALL;
+    const bool all = max_r <= NN_TILE_ALL;
     if (!all && (waves1 >= 4096 || max_r < NN_TILE)) launch_fwd<2, 1>(a, max_q, max_r, nseg, ndirs, st);
     else if (!all && waves1 >= 2048) launch_fwd<2, 2>(a, max_q, max_r, nseg, ndirs, st);
     // whole-set tile over 2048 refs: eight ref groups (512 refs each); 32 x 4096 x 2048 both
@@ -369,13 +366,8 @@ int fwd_dispatch(const NNFwdArgs& a, int nseg, int max_a, int max_b, hipStream_t
 // or query group (QPT queries) for the first index with d == min: the reference's
 // lowest-index tie rule, exactly, with every distance evaluated by the contract formula.
 constexpr int NF_TILE = 512;    // refs per LDS fill (per wave, 6 KiB SoA)
-#ifndef URED_NF_TARGET_WAVES
-#define URED_NF_TARGET_WAVES 4096
-#endif
-#ifndef URED_NF_QPT16_PAIRS
-#define URED_NF_QPT16_PAIRS (1ll << 28)
-#endif
-constexpr int NF_TARGET_WAVES = URED_NF_TARGET_WAVES;
+constexpr int NF_TARGET_WAVES = 4096;            // waves fused_plan aims to give work (16 per CU)
+constexpr long long NF_QPT16_PAIRS = 1ll << 28;  // from this many pairs (and >= 1024 queries): 16 queries per lane
 
 struct NNFusedArgs {
     const float* a; const float* b; const int4* segs;
@@ -598,7 +590,7 @@ FusedPlan fused_plan(int nseg, int max_a, int max_b, int a_total, int b_total) {
     FusedPlan p{};
     if (nseg <= 0 || max_a <= 0 || max_b <= 0) return p;
     const long long pairs = (long long)nseg * max_a * max_b;
-    p.qpt = (pairs >= URED_NF_QPT16_PAIRS && max_a >= 1024) ? 16 : 8;
+    p.qpt = (pairs >= NF_QPT16_PAIRS && max_a >= 1024) ? 16 : 8;
     const int qtile = 64 * p.qpt;
     p.qtiles = (max_a + qtile - 1) / qtile;
     const long long base = (long long)nseg * p.qtiles;

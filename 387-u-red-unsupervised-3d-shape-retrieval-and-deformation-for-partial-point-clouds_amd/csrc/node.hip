@@ -171,9 +171,6 @@ __device__ __forceinline__ void node_colsum(const UredNodeGemmDesc& d, int tile)
     }
 }
 
-#ifndef URED_NODE_WG_PER_CU
-#define URED_NODE_WG_PER_CU 2
-#endif
 // Phase timing build (-DURED_NODE_TIMING=1 -DURED_NTS_M=.. -DURED_NTS_N=.. -DURED_NTS_K=..): launches
 // whose first job has that shape record per workgroup (wave 0) the real-time clock (100 MHz) at start,
 // first chunk landed, MFMA loop end, partial tiles in LDS, stores done (tools/node_phase.py reads
@@ -188,10 +185,10 @@ __device__ unsigned long long ured_nts_buf[NTS_SLOTS * 8];
 #else
 #define URED_NTS(k) do { } while (0)
 #endif
-// two workgroups per CU (the second launch-bounds argument is waves per SIMD: 4 -> <= 128 VGPRs;
-// one accumulator chain per wave, the four waves of a SIMD interleave their MFMAs), so a launch
-// of a few hundred tiles runs in one round
-__global__ __launch_bounds__(NG_NT, URED_NODE_WG_PER_CU * NG_WAVES / 4) void node_gemm_kernel(const NodeJobs jobs) {
+// two workgroups per CU (the second launch-bounds argument is waves per SIMD: 4 -> <= 128 VGPRs),
+// so a launch of a few hundred tiles runs in one round
+constexpr int NODE_WG_PER_CU = 2;
+__global__ __launch_bounds__(NG_NT, NODE_WG_PER_CU * NG_WAVES / 4) void node_gemm_kernel(const NodeJobs jobs) {
     __shared__ float red[NG_WAVES * NG_BM * NG_BN];      // 32 KB: the 8 waves' partial tiles
     int ji = 0;
 #pragma unroll
@@ -213,17 +210,15 @@ __global__ __launch_bounds__(NG_NT, URED_NODE_WG_PER_CU * NG_WAVES / 4) void nod
     unsigned long long nts_[5] = {0, 0, 0, 0, 0};
     URED_NTS(0);
 #endif
-    // URED_NODE_WG_PER_CU 1: two accumulators (even / odd k-steps), independent MFMA chains
-    // summed at the end; 2: one chain (registers for the second resident workgroup)
-    constexpr bool TWO_ACC = URED_NODE_WG_PER_CU == 1;
-    f16v acc0, acc1;
+    // one accumulator chain per wave: the four waves of a SIMD interleave their MFMAs
+    f16v acc;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 
     const LaneSrc sa = lane_a(d, m0 + li);
     const LaneSrc sb = lane_b(d, n0 + li);
     const int nch = (d.K + NG_BK - 1) / NG_BK;
-    float a[16], b[16], an[16], bn[16];
+    float a[16], b[16];
     int c = w;
     if (c < nch) load_chunk(sa, sb, akc, bkc, c * NG_BK, h, d.K, a, b);
 #if URED_NODE_TIMING
@@ -232,32 +227,15 @@ __global__ __launch_bounds__(NG_NT, URED_NODE_WG_PER_CU * NG_WAVES / 4) void nod
 #endif
     while (c < nch) {
         const int cn = c + NG_WAVES;
-        // one chunk of prefetch with one resident workgroup; with two, the other waves of the
-        // SIMD cover the load latency and the registers go to occupancy
-        if (TWO_ACC && cn < nch) load_chunk(sa, sb, akc, bkc, cn * NG_BK, h, d.K, an, bn);
-        if constexpr (TWO_ACC) {
 #pragma unroll
-            for (int j = 0; j < 16; j += 2) {
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j], b[j], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j + 1], b[j + 1], acc1, 0, 0, 0);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 16; ++j) acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j], b[j], acc0, 0, 0, 0);
-        }
-        if (TWO_ACC && cn < nch) {
-#pragma unroll
-            for (int j = 0; j < 16; ++j) { a[j] = an[j]; b[j] = bn[j]; }
-        } else if (!TWO_ACC && cn < nch) {
-            load_chunk(sa, sb, akc, bkc, cn * NG_BK, h, d.K, a, b);
-        }
+        for (int j = 0; j < 16; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j], b[j], acc, 0, 0, 0);
+        // no prefetch: the other waves of the SIMD cover the load latency and the registers go
+        // to the second resident workgroup
+        if (cn < nch) load_chunk(sa, sb, akc, bkc, cn * NG_BK, h, d.K, a, b);
         c = cn;
     }
     URED_NTS(2);
-    f16v accs;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) accs[r] = TWO_ACC ? acc0[r] + acc1[r] : acc0[r];
-    node_partial(red, accs, w, h, li);
+    node_partial(red, acc, w, h, li);
     __syncthreads();
     URED_NTS(3);
 #if URED_NODE_TIMING
@@ -281,7 +259,7 @@ __global__ __launch_bounds__(NG_NT, URED_NODE_WG_PER_CU * NG_WAVES / 4) void nod
 // ---- v4: two K half-chunks in flight per wave --------------------------------------------------
 // v1 loads a wave's next K-chunk only after the current chunk's MFMAs, so a wave with c chunks
 // waits c dependent L2 round trips (tools/node_phase.py: 2.8 us to the first chunk, 3.4 more for the
-// second at 288 x 1536 x 512). v4 keeps URED_NODE_RING half-chunks (16 k per lane pair) in flight:
+// second at 288 x 1536 x 512). v4 keeps NODE_RING half-chunks (16 k per lane pair) in flight:
 // the loads of half q + RING are issued behind the MFMAs of half q, in ring order (sched_barrier), and past
 // the wave's last half it reloads chunk 0 (never consumed), so every iteration issues the same loads
 // and hipcc's wait counts stay exact. Operands are read as raw buffer loads (per-lane byte offset in
@@ -290,14 +268,11 @@ __global__ __launch_bounds__(NG_NT, URED_NODE_WG_PER_CU * NG_WAVES / 4) void nod
 // each has a fixed load count. Same chunk -> wave assignment, MFMA order and fixed-order combine as
 // v1: bitwise v1. Jobs need K, k1 (A2 split) and n1 (B2 split) multiples of 32 and every element
 // below 2^29 of its operand base (node_v4_ok); other launches run v1.
-#ifndef URED_NODE_V4
-#define URED_NODE_V4 1
-#endif
-// half-chunks in flight per wave (3 at most for two strided operands: 16 loads per half). 2: DeformNet
-// fwd+bwd 1.228 ms graph-replayed vs v1 1.276; 4: 1.352 (profiles/r5w_node_v4.log)
-#ifndef URED_NODE_RING
-#define URED_NODE_RING 2
-#endif
+// half-chunks in flight per wave. 2: DeformNet fwd+bwd 1.228 ms graph-replayed vs v1 1.276; 4: 1.352
+// (profiles/r5w_node_v4.log)
+constexpr int NODE_RING = 2;
+// two strided operands issue 16 loads per half: at most ~48 in flight per wave (vmcnt holds 63)
+static_assert(NODE_RING <= 3, "a ring of two strided operands holds at most 3 half-chunks");
 
 struct Src4 {
     const float* base;   // operand base (uniform)
@@ -314,7 +289,7 @@ typedef float f4v __attribute__((ext_vector_type(4)));
 template <bool KC>
 __device__ __forceinline__ void ld8(const Src4& s, int kb, float* out) {
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(s.base), (short)0,
-                                                                        0x7FFFFFFF, 0x00020000);
+                                                                        0x7FFFFFFF, BUF_DWORD3);
 #if URED_DEBUG_BOUNDS
     // the eight elements' last byte lies inside the extent node_v4_ok admitted for this operand
     URED_DBG_CHECK(kb >= 0 && (long long)s.vo + (long long)(KC ? kb * 4 + 28 : (kb + 7) * (long long)s.sk4) + 4 <= s.lim);
@@ -373,7 +348,7 @@ __device__ __forceinline__ void node_ring(const UredNodeGemmDesc& d, const Src4&
     }
 }
 
-__global__ __launch_bounds__(NG_NT, URED_NODE_WG_PER_CU * NG_WAVES / 4) void node_gemm4_kernel(const NodeJobs jobs) {
+__global__ __launch_bounds__(NG_NT, NODE_WG_PER_CU * NG_WAVES / 4) void node_gemm4_kernel(const NodeJobs jobs) {
     __shared__ float red[NG_WAVES * NG_BM * NG_BN];
     int ji = 0;
 #pragma unroll
@@ -428,12 +403,11 @@ __global__ __launch_bounds__(NG_NT, URED_NODE_WG_PER_CU * NG_WAVES / 4) void nod
     f16v acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    // ring depth: at most ~48 loads in flight per wave (the vmcnt counter holds 63)
     switch (J.akc * 2 + J.bkc) {
-        case 3: node_ring<true, true, URED_NODE_RING>(d, a1, a2, bs, w, acc); break;
-        case 2: node_ring<true, false, URED_NODE_RING>(d, a1, a2, bs, w, acc); break;
-        case 1: node_ring<false, true, URED_NODE_RING>(d, a1, a2, bs, w, acc); break;
-        default: node_ring<false, false, (URED_NODE_RING < 3 ? URED_NODE_RING : 3)>(d, a1, a2, bs, w, acc); break;
+        case 3: node_ring<true, true, NODE_RING>(d, a1, a2, bs, w, acc); break;
+        case 2: node_ring<true, false, NODE_RING>(d, a1, a2, bs, w, acc); break;
+        case 1: node_ring<false, true, NODE_RING>(d, a1, a2, bs, w, acc); break;
+        default: node_ring<false, false, NODE_RING>(d, a1, a2, bs, w, acc); break;
     }
     URED_NTS(2);
     node_partial(red, acc, w, h, li);
@@ -460,10 +434,7 @@ __global__ __launch_bounds__(NG_NT, URED_NODE_WG_PER_CU * NG_WAVES / 4) void nod
 // dependent loads per lane; 16 columns x 16 lanes ran 1.2-1.5x longer, tools/node_bn_bench.py);
 // sets processed in order, so the running statistics see the reference's sequence of module
 // calls. fp64 sums, fixed order.
-#ifndef URED_NODE_BN_COLS
-#define URED_NODE_BN_COLS 4
-#endif
-constexpr int BN_COLS = URED_NODE_BN_COLS, BN_RL = 256 / BN_COLS, BN_NT = BN_COLS * BN_RL;
+constexpr int BN_COLS = 4, BN_RL = 256 / BN_COLS, BN_NT = BN_COLS * BN_RL;
 
 __device__ __forceinline__ float bn_in(const float* Y, int ldy, int m, int n, int relu_in) {
     const float y = Y[(long long)m * ldy + n];
@@ -676,7 +647,7 @@ int ured_node_gemm_batch(const UredNodeGemmDesc* const* ds, int n, void* stream)
     }
     if (jobs.njobs == 0) return 0;
     for (int q = jobs.njobs; q <= NG_JOBS; ++q) jobs.tile0[q] = tiles;
-    bool v4 = URED_NODE_V4;
+    bool v4 = true;      // the ring kernel whenever every job qualifies
     for (int q = 0; q < jobs.njobs; ++q) v4 = v4 && node_v4_ok(jobs.job[q].d);
     if (v4) hipLaunchKernelGGL(node_gemm4_kernel, dim3(tiles), dim3(NG_NT), 0, (hipStream_t)stream, jobs);
     else hipLaunchKernelGGL(node_gemm_kernel, dim3(tiles), dim3(NG_NT), 0, (hipStream_t)stream, jobs);

@@ -31,6 +31,12 @@ inline int launch_status(const char* what) {
 
 }  // namespace ured
 
+// Raw buffer descriptors of the MFMA kernels (buffer loads / stores / LDS-DMA at 32-bit offsets).
+constexpr int BUF_DWORD3 = 0x00020000;      // descriptor word 3: raw buffer, gfx9 family (gfx950)
+// A byte offset past any num_records (descriptors here cover < 2 GiB): the hardware drops such a
+// store and returns zeros for such a load, so an out-of-range lane needs a select, not a branch.
+constexpr unsigned BUF_OOB = 0x80000000u;
+
 // Debug build (-DURED_DEBUG_BOUNDS=1): device-side bounds checks of the indices a kernel derives
 // from its arguments or reads from device tables (segment tables, NN indices, labels), of the raw
 // buffer offsets and LDS-DMA ranges of the MFMA kernels, and of their epilogue stores. A violation
