@@ -34,6 +34,9 @@
  *   ured_interp_fwd / ured_interp_bwd <- the three-neighbour inverse-distance interpolation and
  *                       the cat of PointNetFeaturePropagation (pointnet2_utils.py:293-309) and
  *                       their autograd.
+ *   ured_gcn_dirs / ured_gcn_conv_fwd / ured_gcn_conv_bwd / ured_gcn_pool_fwd / ured_gcn_pool_bwd <-
+ *                       get_neighbor_direction_norm, Conv_surface, Conv_layer and Pool_layer of 3D-GCN
+ *                       (network/P_3DGC.py:60-190) and their autograd.
  */
 #ifndef URED_HIP_H
 #define URED_HIP_H
@@ -46,7 +49,7 @@ extern "C" {
 #define URED_EINVAL 1001
 
 /* Library identification: returns URED_ABI_VERSION. */
-#define URED_ABI_VERSION 13  /* 13: ured_interp_fwd / ured_interp_bwd; 12: ured_fps / ured_ball_query / ured_group_fwd / ured_group_bwd; 11: ured_knn_fwd / ured_knn_bwd; 10: ured_occlude; 9: ured_attn_fwd_sets / ured_attn_bwd_sets, ured_get_shape_src_fwd / _bwd; 8: ured_nn_bwd_set; 7: ured_copy_batch; 6: ured_part_rows_bwd_add; 5: node BN SyncBN fields (stats_out/stats_in, sums_out/sums_in); ured_bn_stats et al. */
+#define URED_ABI_VERSION 14  /* 14: ured_gcn_dirs / ured_gcn_conv_fwd / ured_gcn_conv_bwd / ured_gcn_conv_bwd_parts / ured_gcn_pool_fwd / ured_gcn_pool_bwd; 13: ured_interp_fwd / ured_interp_bwd; 12: ured_fps / ured_ball_query / ured_group_fwd / ured_group_bwd; 11: ured_knn_fwd / ured_knn_bwd; 10: ured_occlude; 9: ured_attn_fwd_sets / ured_attn_bwd_sets, ured_get_shape_src_fwd / _bwd; 8: ured_nn_bwd_set; 7: ured_copy_batch; 6: ured_part_rows_bwd_add; 5: node BN SyncBN fields (stats_out/stats_in, sums_out/sums_in); ured_bn_stats et al. */
 int ured_abi_version(void);
 /* Thread-local message for the last failing call on this thread ("" if none). */
 const char* ured_last_error(void);
@@ -589,6 +592,59 @@ int ured_interp_fwd(const float* points2, const int* idx, const float* d2, const
  * forward's. */
 int ured_interp_bwd(const float* grad_out, const float* points2, const int* idx, const float* w, const float* d2, int B,
                     int N, int S, int K, int D1, int D2, float* grad_points2, float* grad_d2, void* stream);
+
+/* ---------------- 3D-GCN graph convolution (csrc/gcn.hip) ---------------- */
+/* Conv_surface, Conv_layer and Pool_layer of network/P_3DGC.py without their [B, V, n, S*C] tensors.
+ * Activations are point-major fp32 rows [B*V, .]; idx int32 [B,V,n] holds rows of the same cloud.
+ * An index outside [0,V) reads as a zero row (ured_gcn_dirs: a zero direction) and takes no
+ * gradient. Limits of all entry points: V, C >= 1, 1 <= n (k) <= URED_GCN_NMAX (the winning slot is
+ * stored as a uint8), 1 <= S <= URED_GCN_SMAX (a lane keeps its 3 * S support components in
+ * registers), B <= 65535, B * V * (S + 1) * C < 2^31, B * V * n * 3 < 2^31. B = 0 is a no-op. */
+#define URED_GCN_NMAX 255
+#define URED_GCN_SMAX 8
+/* get_neighbor_direction_norm (:60-69). vertices [B,V,3] -> out [B,V,n,3]:
+ *   d = vertices[b, idx[b,v,j]] - vertices[b,v]; out = d / max(sqrt(((d.x*d.x) + (d.y*d.y)) + (d.z*d.z)), 1e-12f)
+ * (IEEE sqrt and division); a coincident neighbour gives the zero vector. */
+int ured_gcn_dirs(const float* vertices, const int* idx, int B, int V, int n, float* out, void* stream);
+/* The fused convolution. dirn [B,V,n,3], sdn [3, S*C], feat [B*V, (S+1)*C] or NULL, idx [B,V,n] ->
+ * out [B*V, C], slot uint8 [B*V, S, C]:
+ *   theta = max(((d.x*a.x) + (d.y*a.y)) + (d.z*a.z), 0), d = dirn[b,v,j,:], a = sdn[:, s*C + c]
+ *   with feat (Conv_layer, :136-163): m_s = max_j theta * feat[b, idx[b,v,j], C + s*C + c],
+ *        out[b,v,c] = feat[b,v,c] + ((m_0 + m_1) + ... + m_{S-1})
+ *   feat NULL (Conv_surface, :88-112): m_s = max_j theta, out[b,v,c] = (m_0 + m_1) + ... + m_{S-1}
+ * in fp32 without FMA contraction; slot[b,v,s,c] is the lowest j that attains m_s. One launch. */
+int ured_gcn_conv_fwd(const float* dirn, const float* sdn, const float* feat, const int* idx, int B, int V, int n, int S,
+                      int C, float* out, unsigned char* slot, void* stream);
+/* Its backward from grad_out [B*V, C], WRITTEN (every element of both outputs is set), with
+ * j* = slot[b,v,s,c], theta* the forward's theta at j* (relu passes a gradient iff theta* > 0):
+ *   grad_feat [B*V, (S+1)*C] (NULL exactly when feat is): columns 0..C-1 a copy of grad_out; element
+ *     (b, r, C + s*C + c) the sum over the (v, j) with idx[b,v,j] = r and j = j* of
+ *     grad_out[b,v,c] * theta*, in fp32 from 0 in ascending (v, j) order;
+ *   grad_sdn [3, S*C]: element (k, s*C + c) the sum over the vertices with theta* > 0 of
+ *     (grad_out[b,v,c] * f) * dirn[b,v,j*,k], f = feat[b, idx[b,v,j*], C + s*C + c] (1 without
+ *     feat): ured_gcn_conv_bwd_parts(B, V) workgroups sum ranges of consecutive vertices (four
+ *     interleaved sequences each, combined in a fixed order) into rows of ws, which are added in
+ *     ascending order.
+ * No atomics; a second run is bitwise identical. ws: ured_gcn_conv_bwd_parts(B, V) * 3 * S * C floats
+ * (ws_floats: its size, checked); parts = clamp(ceil(B * V / URED_GCN_BWD_ROWS), 1, URED_GCN_BWD_PARTS).
+ * Further limit: V * n < 2^31. Three launches (two without feat). */
+#define URED_GCN_BWD_ROWS 16
+#define URED_GCN_BWD_PARTS 512
+int ured_gcn_conv_bwd_parts(int B, int V);
+int ured_gcn_conv_bwd(const float* grad_out, const float* dirn, const float* sdn, const float* feat, const int* idx,
+                      const unsigned char* slot, int B, int V, int n, int S, int C, float* grad_feat, float* grad_sdn,
+                      float* ws, size_t ws_floats, void* stream);
+/* Pool_layer's pooling for the sampled vertices only (:172-190). feat [B*V, C], idx int32 [B,V,k],
+ * sample int32 [P] (vertex ids, the same for every cloud) -> out [B*P, C], slot uint8 [B*P, C]:
+ *   out[b,p,c] = max_j feat[b, idx[b, sample[p], j], c], slot the lowest j that attains it.
+ * A sample outside [0,V) gives a zero row and no gradient. Limits: V, C >= 1, 1 <= k <= URED_GCN_NMAX,
+ * B <= 65535, B * V * C, B * P * C, B * V * k and P * k < 2^31. */
+int ured_gcn_pool_fwd(const float* feat, const int* idx, const int* sample, int B, int V, int k, int P, int C, float* out,
+                      unsigned char* slot, void* stream);
+/* Its backward, WRITTEN: grad_feat[b,r,c] = the sum over the (p, j) with idx[b, sample[p], j] = r and
+ * slot[b,p,c] = j of grad_out[b,p,c], in fp32 from 0 in ascending (p, j) order. No atomics. */
+int ured_gcn_pool_bwd(const float* grad_out, const int* idx, const int* sample, const unsigned char* slot, int B, int V,
+                      int k, int P, int C, float* grad_feat, void* stream);
 
 /* ---------------- loss head (csrc/loss.hip) ---------------- */
 /* compute_cm_loss of the deformed shape `out` [B,S,3] and of its mirror image (x -> -x,
