@@ -14,6 +14,7 @@
   group    PointNet++ set abstraction primitives: farthest-point sampling, ball query, grouping (GroupFn)
   interp   PointNet++ feature propagation: three_nn and the inverse-distance interpolation (InterpFn)
   gcn      3D-GCN graph convolution: neighbor_dirs, GcnConvFn, GcnPoolFn, GcnLinearFn
+  vn       Vector-Neuron DGCNN layers: knn_rows, VnEdgeFn, VnPointFn, VnMaxPoolFn, VnFrameFn, VnLinearFn
   losshead the step's loss head (chamfer families, contrastive, residual, reconstruction, weighted sum)
 """
-from . import _lib, attn, gcn, group, interp, kernels, losshead, nn, node, occ, ops, optim, syncbn  # noqa: F401
+from . import _lib, attn, gcn, group, interp, kernels, losshead, nn, node, occ, ops, optim, syncbn, vn  # noqa: F401

@@ -37,6 +37,10 @@
  *   ured_gcn_dirs / ured_gcn_conv_fwd / ured_gcn_conv_bwd / ured_gcn_pool_fwd / ured_gcn_pool_bwd <-
  *                       get_neighbor_direction_norm, Conv_surface, Conv_layer and Pool_layer of 3D-GCN
  *                       (network/P_3DGC.py:60-190) and their autograd.
+ *   ured_vn_knn / ured_vn_act_fwd / ured_vn_act_bwd / ured_vn_maxpool_fwd / ured_vn_maxpool_bwd /
+ *   ured_vn_frame_fwd / ured_vn_frame_bwd <- knn and get_graph_feature (network/VN/vn_dgcnn_util.py:11-47),
+ *                       VNLinearLeakyReLU, VNBatchNorm, VNMaxPool and VNStdFeature's einsum
+ *                       (network/VN/vn_layers.py:48-77, 112-149, 199) and their autograd.
  */
 #ifndef URED_HIP_H
 #define URED_HIP_H
@@ -49,7 +53,7 @@ extern "C" {
 #define URED_EINVAL 1001
 
 /* Library identification: returns URED_ABI_VERSION. */
-#define URED_ABI_VERSION 14  /* 14: ured_gcn_dirs / ured_gcn_conv_fwd / ured_gcn_conv_bwd / ured_gcn_conv_bwd_parts / ured_gcn_pool_fwd / ured_gcn_pool_bwd; 13: ured_interp_fwd / ured_interp_bwd; 12: ured_fps / ured_ball_query / ured_group_fwd / ured_group_bwd; 11: ured_knn_fwd / ured_knn_bwd; 10: ured_occlude; 9: ured_attn_fwd_sets / ured_attn_bwd_sets, ured_get_shape_src_fwd / _bwd; 8: ured_nn_bwd_set; 7: ured_copy_batch; 6: ured_part_rows_bwd_add; 5: node BN SyncBN fields (stats_out/stats_in, sums_out/sums_in); ured_bn_stats et al. */
+#define URED_ABI_VERSION 15  /* 15: ured_vn_parts / ured_vn_knn / ured_vn_act_fwd / ured_vn_act_bwd / ured_vn_maxpool_fwd / ured_vn_maxpool_bwd / ured_vn_frame_fwd / ured_vn_frame_bwd; 14: ured_gcn_dirs / ured_gcn_conv_fwd / ured_gcn_conv_bwd / ured_gcn_conv_bwd_parts / ured_gcn_pool_fwd / ured_gcn_pool_bwd; 13: ured_interp_fwd / ured_interp_bwd; 12: ured_fps / ured_ball_query / ured_group_fwd / ured_group_bwd; 11: ured_knn_fwd / ured_knn_bwd; 10: ured_occlude; 9: ured_attn_fwd_sets / ured_attn_bwd_sets, ured_get_shape_src_fwd / _bwd; 8: ured_nn_bwd_set; 7: ured_copy_batch; 6: ured_part_rows_bwd_add; 5: node BN SyncBN fields (stats_out/stats_in, sums_out/sums_in); ured_bn_stats et al. */
 int ured_abi_version(void);
 /* Thread-local message for the last failing call on this thread ("" if none). */
 const char* ured_last_error(void);
@@ -645,6 +649,94 @@ int ured_gcn_pool_fwd(const float* feat, const int* idx, const int* sample, int 
  * slot[b,p,c] = j of grad_out[b,p,c], in fp32 from 0 in ascending (p, j) order. No atomics. */
 int ured_gcn_pool_bwd(const float* grad_out, const int* idx, const int* sample, const unsigned char* slot, int B, int V,
                       int k, int P, int C, float* grad_feat, void* stream);
+
+/* ---------------- Vector-Neuron DGCNN layers (csrc/vn.hip) ---------------- */
+/* get_graph_feature + VNLinearLeakyReLU, VNMaxPool, VNStdFeature's frame product and the feature-space
+ * kNN of network/VN/ without the [B, 2C, 3, N, k] tensors of the torch composition. A VN feature is
+ * point-major with the channel innermost, [B, N, 3, C] fp32 (so [B*N*3, C] is a GEMM operand); idx
+ * int32 [B,N,k] holds rows of the same cloud; an index outside [0,N) reads as a zero row and takes no
+ * gradient. fp32 without FMA contraction, IEEE sqrt and division. No float atomics anywhere; a
+ * second run of any entry point is bitwise identical. B = 0 (rows = 0) is a no-op. */
+#define URED_VN_KMAX 32      /* neighbours per point */
+#define URED_VN_DMAX 256     /* dimensions of ured_vn_knn (the encoders use 3, 63 and 126) */
+#define URED_VN_COMAX 384    /* output channels: a wave keeps 6 chunks of 64 channels in registers */
+#define URED_VN_STAT_ROWS 16
+#define URED_VN_PARTS 256
+/* Partial rows of the BatchNorm workspaces: clamp(ceil(B * N / URED_VN_STAT_ROWS), 1, URED_VN_PARTS). */
+int ured_vn_parts(int B, int N);
+/* Self-kNN inside each cloud in D dimensions. x [B,N,D] -> idx int32 [B,N,K]: the K rows of the same
+ * cloud nearest to row n, the row itself included, sorted by (distance, index):
+ *   dist(n, i) = (...((0 + e_0*e_0) + e_1*e_1) + ...) + e_{D-1}*e_{D-1},  e_d = x[b,i,d] - x[b,n,d]
+ * and of two candidates at the same distance the lower index comes first. ws: B * N * N floats (ws_floats:
+ * its size, checked), the clouds' distance matrices, written by the first of the two launches (64 x 64
+ * tiles through LDS) and read by the second (one wave per row, K rounds of a lexicographic minimum).
+ * A row with fewer than K comparable distances (NaN input) ends in -1 entries. Limits: N >= 1,
+ * 1 <= D <= URED_VN_DMAX, 1 <= K <= min(N, URED_VN_KMAX), B <= 65535, N <= 64 * 65535,
+ * B * N * max(D, K) < 2^31. */
+int ured_vn_knn(const float* x, int B, int N, int D, int K, int* idx, float* ws, size_t ws_floats, void* stream);
+/* The normalise + directional leaky ReLU pair of VNLinearLeakyReLU (vn_layers.py:48-77, VNBatchNorm
+ * :112-132) after its two linear maps, which the caller runs as one per-point GEMM:
+ *   edge form  (idx != NULL; get_graph_feature, vn_dgcnn_util.py:20-47, + dim = 5): the maps act on
+ *     [x_j - x_i, x_i], so W . edge = W_a x_j + (W_b - W_a) x_i and
+ *     uv [B*N*3, 2W] = x [B*N*3, C] @ [Wf_a; Wd_a; Wf_b - Wf_a; Wd_b - Wd_a]^T, W = Co + Cd, columns
+ *     [Uf (Co) | Ud (Cd) | Vf (Co) | Vd (Cd)];  p = Uf[b, idx[b,n,j]] + Vf[b,n], d = Ud[b, idx[b,n,j]] + Vd[b,n]
+ *   point form (idx == NULL, k = 1; dim = 4): uv [B*N*3, W] = [P (Co) | D (Cd)], p = P[b,n], d = D[b,n]
+ *   Cd = Co (map_to_dir per channel) or 1 (share_nonlinearity).
+ * Per (b, n, j, c), p and d in R^3:
+ *   nrm = sqrt(((p.x*p.x) + (p.y*p.y)) + (p.z*p.z)) + 1e-6f
+ *   nb  = nrm * scale[c] + shift[c],  scale = gamma * invstd, shift = beta - mean * scale
+ *   ph  = (p / nrm) * nb
+ *   t   = ((ph.x*d.x) + (ph.y*d.y)) + (ph.z*d.z),  q = (((d.x*d.x) + (d.y*d.y)) + (d.z*d.z)) + 1e-6f
+ *   mask = t >= 0,  o = mask ? ph : 0.2f * ph + 0.8f * (ph - (t / q) * d)
+ *   pool_mean: out [B,N,3,Co] = (the sum of o over ascending j from 0) / k;  else out [B,N,k,3,Co] = o
+ * mask uint8 [B,N,k,Co] is the branch taken. training: mean and biased variance of nrm over all
+ * B*N*k edges per channel, summed in float64 (ured_vn_parts(B, N) workgroups over ranges of
+ * consecutive points, four interleaved sequences each, combined in a fixed order, the partial rows
+ * added in ascending order), invstd = 1 / sqrt(var + eps); running_mean / running_var (unbiased) move
+ * by `momentum` and *num_batches_tracked grows by 1 as in nn.BatchNorm (each may be NULL); needs
+ * B*N*k > 1. eval: mean / var are the running statistics. stat [4, Co] receives mean, invstd,
+ * scale, shift (the backward reads it). ws: ured_vn_parts(B, N) * 2 * Co doubles (training only;
+ * ws_doubles: its size, checked). Limits: N >= 1, 1 <= k <= URED_VN_KMAX, 1 <= Co <= URED_VN_COMAX,
+ * B <= 65535, B * N * k * 6 * (Co + Cd) < 2^31. Three launches (two in eval). */
+int ured_vn_act_fwd(const float* uv, const int* idx, int B, int N, int k, int Co, int Cd, int training, const float* gamma,
+                    const float* beta, float* running_mean, float* running_var, long long* num_batches_tracked,
+                    float momentum, float eps, int pool_mean, double* ws, size_t ws_doubles, float* stat, float* out,
+                    unsigned char* mask, void* stream);
+/* Its backward from grad_out (the shape of out), WRITTEN (every element of every output is set). The
+ * branch is read from mask, not recomputed. With go the gradient of o (grad_out / k under pool_mean):
+ *   mask: g_ph = go, g_d = 0;  else s = t / q, gs = -0.8f * (go . d), gt = gs / q:
+ *         g_ph = go + gt * d,  g_d = ((-0.8f * s) * go + gt * ph) + (2 * -(gt * s)) * d
+ *   g_nb = (g_ph . p) / nrm,  nhat = (nrm - mean) * invstd
+ *   grad_beta [Co] = sum g_nb, grad_gamma [Co] = sum g_nb * nhat (float64 sums, the forward's order)
+ *   g_nrm = -((g_ph . p) * nb) / (nrm * nrm) + scale * ((g_nb - m1) - nhat * m2), m1 / m2 the means
+ *           of g_nb / g_nb * nhat over the edges in training and 0 in eval (coef [2, Co] receives them)
+ *   g_p = g_ph * (nb / nrm) + g_nrm * (p / |p|)   (the second term is 0 at p = 0, as torch.norm's)
+ * grad_uv (the shape of uv): the V (point form: all) columns of row (b,n) are the sums of g_p / g_d
+ * over ascending j (a shared direction's g_d summed over the lane's channels in ascending order, then
+ * across the wave by a fixed butterfly); the U columns of row (b,r) are the sums over the (n, j)
+ * with idx[b,n,j] = r in ascending (n, j) order, read from edge_ws [B*N*k, 3, W], the per-edge
+ * (g_p | g_d) that the call writes first (edge form only; edge_ws_floats: its size, checked).
+ * ws as in the forward. Further limit: N * k < 2^31. Four launches (three in the point form). */
+int ured_vn_act_bwd(const float* grad_out, const float* uv, const int* idx, const unsigned char* mask, int B, int N, int k,
+                    int Co, int Cd, int training, int pool_mean, const float* stat, double* ws, size_t ws_doubles, float* coef,
+                    float* edge_ws, size_t edge_ws_floats, float* grad_uv, float* grad_gamma, float* grad_beta, void* stream);
+/* VNMaxPool (vn_layers.py:135-149) after its linear map. x, d [B,N,k,3,C] -> out [B,N,3,C], slot uint8
+ * [B,N,C]: the j with the largest ((x.x*d.x) + (x.y*d.y)) + (x.z*d.z), the lowest j on a tie;
+ * out[b,n,:,c] = x[b,n,slot,:,c]. Limits: N, C >= 1, 1 <= k <= URED_VN_KMAX, B * N * k * 3 * C < 2^31. */
+int ured_vn_maxpool_fwd(const float* x, const float* d, int B, int N, int k, int C, float* out, unsigned char* slot,
+                        void* stream);
+/* Its backward, WRITTEN: grad_x[b,n,j,:,c] = j == slot[b,n,c] ? grad_out[b,n,:,c] : 0 (d takes no
+ * gradient, as in the reference, whose index selection cuts it off). */
+int ured_vn_maxpool_bwd(const float* grad_out, const unsigned char* slot, int B, int N, int k, int C, float* grad_x,
+                        void* stream);
+/* VNStdFeature's einsum('bijm,bjkm->bikm') (vn_layers.py:199). x [rows,3,C], z [rows,3,3] (z[r,j,kk]) ->
+ *   out[r,kk,c] = ((x[r,0,c]*z[r,0,kk]) + (x[r,1,c]*z[r,1,kk])) + (x[r,2,c]*z[r,2,kk])
+ * Backward, WRITTEN: grad_x[r,j,c] = ((g[r,0,c]*z[r,j,0]) + (g[r,1,c]*z[r,j,1])) + (g[r,2,c]*z[r,j,2]);
+ * grad_z[r,j,kk] = sum_c x[r,j,c] * g[r,kk,c], per lane over c = lane, lane + 64, ... and then across
+ * the wave by a fixed butterfly. Limits: C >= 1, rows * 3 * C < 2^31. */
+int ured_vn_frame_fwd(const float* x, const float* z, int rows, int C, float* out, void* stream);
+int ured_vn_frame_bwd(const float* grad_out, const float* x, const float* z, int rows, int C, float* grad_x, float* grad_z,
+                      void* stream);
 
 /* ---------------- loss head (csrc/loss.hip) ---------------- */
 /* compute_cm_loss of the deformed shape `out` [B,S,3] and of its mirror image (x -> -x,
