@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libured_hip.so"
 # URED_LIB: an alternative build of the same ABI (A/B kernel experiments, tools/)
 LIB_PATH = os.environ.get("URED_LIB") or os.path.join(_HERE, LIB_NAME)
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -42,6 +42,8 @@ _SIGNATURES = {
     "ured_nn_seg_fwd_ws": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _SZ, _P],
     "ured_nn_seg_bwd": [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
     "ured_dcd": [_P, _P, _P, _P, _I, _I, _I, _F, _I, _F, _F, _P, _P, _P, _P],
+    "ured_dcd_loss_fwd": [_P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P],
+    "ured_dcd_loss_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P],
     "ured_knn_fwd": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "ured_knn_bwd": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
 }

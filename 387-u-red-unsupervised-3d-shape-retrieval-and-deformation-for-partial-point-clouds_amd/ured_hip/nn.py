@@ -239,7 +239,8 @@ DCD_MAX_POINTS = 16384
 def dcd(dist1, idx1, dist2, idx2, alpha=1000.0, n_lambda=1, frac_12=None, frac_21=None):
     """Fused density-aware chamfer tail (calc_dcd, utils_v2/model_utils.py:13-51) on dense NN
     outputs: dist1/idx1 [b,n1] gt -> x, dist2/idx2 [b,n2] x -> gt (from nn_dense(gt, x)).
-    Returns (loss [b], cd_p [b], cd_t [b]); forward only."""
+    Returns (loss [b], cd_p [b], cd_t [b]); forward only. An integral n_lambda runs ured_dcd, any
+    other one ured_dcd_loss_fwd (a float exponent) with cd_p / cd_t requested: one launch either way."""
     b, n1 = dist1.shape
     n2 = dist2.shape[1]
     frac_12 = n2 / n1 if frac_12 is None else frac_12
@@ -248,6 +249,11 @@ def dcd(dist1, idx1, dist2, idx2, alpha=1000.0, n_lambda=1, frac_12=None, frac_2
     dist1, dist2 = dist1.contiguous(), dist2.contiguous()
     idx1, idx2 = idx1.to(torch.int32).contiguous(), idx2.to(torch.int32).contiguous()
     out = torch.empty(3, b, device=dist1.device, dtype=torch.float32)
+    if float(n_lambda) != int(n_lambda):
+        _lib.call("ured_dcd_loss_fwd", _lib.ptr(dist1), _lib.ptr(idx1), _lib.ptr(dist2), _lib.ptr(idx2), b, n1, n2,
+                  float(alpha), float(n_lambda), float(frac_12), float(frac_21),
+                  _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]), None, None, _lib.stream_of(dist1))
+        return out[0], out[1], out[2]
     _lib.call("ured_dcd", _lib.ptr(dist1), _lib.ptr(idx1), _lib.ptr(dist2), _lib.ptr(idx2), b, n1, n2,
               float(alpha), int(n_lambda), float(frac_12), float(frac_21),
               _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.stream_of(dist1))

@@ -41,6 +41,11 @@
  *   ured_vn_frame_fwd / ured_vn_frame_bwd <- knn and get_graph_feature (network/VN/vn_dgcnn_util.py:11-47),
  *                       VNLinearLeakyReLU, VNBatchNorm, VNMaxPool and VNStdFeature's einsum
  *                       (network/VN/vn_layers.py:48-77, 112-149, 199) and their autograd.
+ *   ured_dcd_loss_fwd / ured_dcd_loss_bwd <- the torch tail of calc_dcd under autograd
+ *                       (Density_aware_Chamfer_Distance/utils_v2/model_utils.py:13-51) and its autograd.
+ *   ured_pcn_relu / ured_pcn_pool_bwd / ured_pcn_fold_fwd / ured_pcn_fold_bwd / ured_pcn_center_fwd /
+ *   ured_pcn_center_bwd <- the ReLUs, max-pools, concatenations and the `+ center` of PCN_encoder /
+ *                       PCN_decoder (Density_aware_Chamfer_Distance/models/pcn.py:13-71) and their autograd.
  */
 #ifndef URED_HIP_H
 #define URED_HIP_H
@@ -53,7 +58,7 @@ extern "C" {
 #define URED_EINVAL 1001
 
 /* Library identification: returns URED_ABI_VERSION. */
-#define URED_ABI_VERSION 15  /* 15: ured_vn_parts / ured_vn_knn / ured_vn_act_fwd / ured_vn_act_bwd / ured_vn_maxpool_fwd / ured_vn_maxpool_bwd / ured_vn_frame_fwd / ured_vn_frame_bwd; 14: ured_gcn_dirs / ured_gcn_conv_fwd / ured_gcn_conv_bwd / ured_gcn_conv_bwd_parts / ured_gcn_pool_fwd / ured_gcn_pool_bwd; 13: ured_interp_fwd / ured_interp_bwd; 12: ured_fps / ured_ball_query / ured_group_fwd / ured_group_bwd; 11: ured_knn_fwd / ured_knn_bwd; 10: ured_occlude; 9: ured_attn_fwd_sets / ured_attn_bwd_sets, ured_get_shape_src_fwd / _bwd; 8: ured_nn_bwd_set; 7: ured_copy_batch; 6: ured_part_rows_bwd_add; 5: node BN SyncBN fields (stats_out/stats_in, sums_out/sums_in); ured_bn_stats et al. */
+#define URED_ABI_VERSION 16  /* 16: ured_dcd_loss_fwd / ured_dcd_loss_bwd, ured_pcn_relu / ured_pcn_pool_bwd / ured_pcn_fold_fwd / ured_pcn_fold_bwd / ured_pcn_center_fwd / ured_pcn_center_bwd; 15:ured_vn_parts / ured_vn_knn / ured_vn_act_fwd / ured_vn_act_bwd / ured_vn_maxpool_fwd / ured_vn_maxpool_bwd / ured_vn_frame_fwd / ured_vn_frame_bwd; 14: ured_gcn_dirs / ured_gcn_conv_fwd / ured_gcn_conv_bwd / ured_gcn_conv_bwd_parts / ured_gcn_pool_fwd / ured_gcn_pool_bwd; 13: ured_interp_fwd / ured_interp_bwd; 12: ured_fps / ured_ball_query / ured_group_fwd / ured_group_bwd; 11: ured_knn_fwd / ured_knn_bwd; 10: ured_occlude; 9: ured_attn_fwd_sets / ured_attn_bwd_sets, ured_get_shape_src_fwd / _bwd; 8: ured_nn_bwd_set; 7: ured_copy_batch; 6: ured_part_rows_bwd_add; 5: node BN SyncBN fields (stats_out/stats_in, sums_out/sums_in); ured_bn_stats et al. */
 int ured_abi_version(void);
 /* Thread-local message for the last failing call on this thread ("" if none). */
 const char* ured_last_error(void);
@@ -202,6 +207,28 @@ int ured_nn_seg_bwd(const float* a, const float* b, const int* segs, int nseg,
 int ured_dcd(const float* dist1, const int* idx1, const float* dist2, const int* idx2, int b, int n1, int n2,
              float alpha, int n_lambda, float frac_12, float frac_21, float* loss, float* cd_p, float* cd_t,
              void* stream);
+
+/* The same reduction as a training loss (calc_dcd under autograd). The exponent is a float:
+ * count^lambda is 1, c, c*c or sqrtf(c) for lambda = 0, 1, 2, 0.5 and powf(c, lambda) otherwise;
+ * for those integral lambdas loss / cd_p / cd_t equal ured_dcd's bit for bit. cd_p and cd_t may be
+ * NULL. coef1 [b,n1] / coef2 [b,n2] (each may be NULL) receive the derivative of the item's loss
+ * with respect to each squared distance, the weights detached as in the reference
+ * (model_utils.py:35,41):
+ *   coef1[j] = alpha exp(-alpha d1[j]) w1[j] / (2 n1),  coef2[j] = alpha exp(-alpha d2[j]) w2[j] / (2 n2).
+ * Deterministic; n1 + n2 <= 16384, lambda >= 0, checked before any device work. */
+int ured_dcd_loss_fwd(const float* dist1, const int* idx1, const float* dist2, const int* idx2, int b, int n1, int n2,
+                      float alpha, float lambda, float frac_12, float frac_21, float* loss, float* cd_p, float* cd_t,
+                      float* coef1, float* coef2, void* stream);
+/* Its backward, ONE launch for both point sets: xyz1 [b,n1,3] = gt, xyz2 [b,n2,3] = x, the
+ * indices and coefficients of the forward. The gradient of squared distance j of item i is
+ *   g1[j] = g_loss[i] coef1[j] + gd1[j]   (g_loss NULL: no gradient through the loss;
+ *                                          gd1 / gd2 NULL: no further gradient of dist1 / dist2)
+ * and goes through the gather form of ured_nn_bwd_set (own term first, then the other side's
+ * entries in ascending index; no float atomics). Every element of gxyz1 [b,n1,3] / gxyz2 [b,n2,3]
+ * is WRITTEN; a NULL output skips that side. */
+int ured_dcd_loss_bwd(const float* xyz1, const float* xyz2, const int* idx1, const int* idx2, const float* coef1,
+                      const float* coef2, const float* g_loss, const float* gd1, const float* gd2, int b, int n1,
+                      int n2, float* gxyz1, float* gxyz2, void* stream);
 
 /* ---------------- per-point MLP (1x1 conv) on fp32 MFMA ---------------- *
  * Replaces the Conv1d(k=1)+BatchNorm1d+ReLU chains of TargetEncoder
@@ -737,6 +764,30 @@ int ured_vn_maxpool_bwd(const float* grad_out, const unsigned char* slot, int B,
 int ured_vn_frame_fwd(const float* x, const float* z, int rows, int C, float* out, void* stream);
 int ured_vn_frame_bwd(const float* grad_out, const float* x, const float* z, int rows, int C, float* grad_x, float* grad_z,
                       void* stream);
+
+/* ---------------- PCN completion network (csrc/pcn.hip) ---------------- */
+/* The pieces of models/pcn.py that are not GEMMs; activations point-major [rows][C] fp32.
+ * ured_pcn_relu: out[i] = max(y[i], 0), or with g: out[i] = y[i] > 0 ? g[i] : 0 (n elements).
+ * ured_pcn_pool_bwd: backward of pooled[grp][c] = max over the `rows` rows of group grp of Y [G*rows][C],
+ *   win [G][C] the winning global row (lowest index on a tie): accumulate 0 WRITES every element of
+ *   dY (g at the winner, 0 elsewhere); accumulate 1 adds g at the winners only. A winner outside its
+ *   group is never written.
+ * ured_pcn_fold_fwd: Y[((b*num_coarse + c)*scale + s)][ch] = (Gb[b][ch] + Pc[b*num_coarse + c][ch]) + Gs[s][ch]
+ *   (the decoder's conv1 pre-activation; Gb [B][C] carries the bias).
+ * ured_pcn_fold_bwd: with G = dH where Y > 0 else 0 (both [B*num_coarse*scale][C]):
+ *   dPc[p][ch] = sum_s G[p*scale + s][ch] (s ascending), WRITTEN; ws[k][s][ch] = the sum of G[p*scale + s][ch]
+ *   over the points p (ascending) of chunk k = p / chunk, WRITTEN ([ceil(B*num_coarse / chunk)][scale][C]).
+ *   scale <= 16. No float atomics.
+ * ured_pcn_center_fwd: out[r][k] = y[r][k] + cp[r / scale][k] over [B*num_coarse*scale][3].
+ * ured_pcn_center_bwd: out[q][k] = sum_s dF[q*scale + s][k] (s ascending) (+ add[q][k]) over [B*num_coarse][3]. */
+int ured_pcn_relu(const float* y, const float* g, long long n, float* out, void* stream);
+int ured_pcn_pool_bwd(const float* g, const int* win, int G, int rows, int C, float* dY, int accumulate, void* stream);
+int ured_pcn_fold_fwd(const float* Gb, const float* Pc, const float* Gs, int B, int num_coarse, int scale, int C, float* Y,
+                      void* stream);
+int ured_pcn_fold_bwd(const float* dH, const float* Y, int B, int num_coarse, int scale, int C, int chunk, float* dPc,
+                      float* ws, void* stream);
+int ured_pcn_center_fwd(const float* y, const float* cp, int B, int num_coarse, int scale, float* out, void* stream);
+int ured_pcn_center_bwd(const float* dF, const float* add, int B, int num_coarse, int scale, float* out, void* stream);
 
 /* ---------------- loss head (csrc/loss.hip) ---------------- */
 /* compute_cm_loss of the deformed shape `out` [B,S,3] and of its mirror image (x -> -x,
