@@ -6,7 +6,9 @@ plan the device returned (its float fields are fed to the oracle, so the compari
 on sqrt / sin / cos rounding); the drawn plan itself is compared separately. point_occ, occ_mean
 and occ_rot are compared with the float64 oracle at atol 2e-6 for coordinates in [-1, 1] (one
 rounding of an fp64 mean, one subtraction, a 3x3 product: each ~1e-7)."""
+import ctypes
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -19,6 +21,20 @@ pytestmark = pytest.mark.gpu
 
 ATOL = 2e-6
 MAX_ERR = {"v": 0.0}
+
+
+@pytest.fixture(autouse=True)
+def _occ_debug_word():
+    """The debug build's bounds word of occ.hip (file id 11), read and cleared after each test."""
+    yield
+    mod = sys.modules.get("ured_hip._lib")
+    if mod is None or mod._lib is None or not hasattr(mod._lib, "ured_dbg_occ"):
+        return
+    fn = mod._lib.ured_dbg_occ
+    fn.restype, fn.argtypes = ctypes.c_ulonglong, [ctypes.c_int]
+    torch.cuda.synchronize()
+    v = fn(1)
+    assert not v, f"device-side bounds check violated (debug build): occ.hip:{v & 0xFFFFFFFF}"
 
 
 def cloud(B, N, seed, nsem=4):

@@ -38,6 +38,24 @@ def test_part_aabb_rejects_cpu():
         part_aabb(pb)
 
 
+def test_seg_aabb_wave_and_block_edges(dev):
+    """ured_seg_aabb on one flat cloud whose segments end at the wave (63 / 64 / 65) and block
+    (255 / 256 / 257) edges of its 256-thread reduction, one longer than three trips, and empty
+    segments first and last: bit-exact against compute_aabbox per segment, zeros where empty."""
+    from ured_hip import _lib
+    lens = [0, 1, 63, 64, 65, 255, 256, 257, 1000, 0]
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    g = torch.Generator().manual_seed(17)
+    x = torch.rand(int(off[-1]), 3, generator=g) * 2 - 1
+    xd, od = x.to(dev), torch.from_numpy(off).to(dev)
+    out = torch.full((len(lens), 6), float("nan"), device=dev)
+    _lib.call("ured_seg_aabb", _lib.ptr(xd), _lib.ptr(od), len(lens), _lib.ptr(out), _lib.stream_of(xd))
+    got = out.cpu()
+    for s, n in enumerate(lens):
+        exp = _aabb_ref(x[off[s]:off[s + 1]]) if n else torch.zeros(6)
+        assert torch.equal(got[s], exp), (s, n)
+
+
 def test_get_shape_hip_matches_bmm(dev):
     """get_shape's HIP GEMV (ured_get_shape_fwd/bwd) vs the float64 torch.bmm of the reference
     formula (dataset_utils.py:691-726), values and the gradient w.r.t. the params; deterministic."""
@@ -88,7 +106,14 @@ def test_get_shape_src_equals_gathered(dev, with_dflt):
     assert torch.equal(a.grad, b.grad)
 
 
-@pytest.mark.parametrize("B,N,P,C,kmax", [(16, 2048, 16, 512, 4), (3, 700, 16, 6, 16), (2, 5, 8, 3, 8)])
+# row widths at the kernel's edges: 1 and 257 (scalar lanes; 257 >= 256: one row per block, strided
+# columns), 4 (one float4 lane per row), 20 and 252 (5 and 63 float4 lanes: 256 % lanes != 0, idle tail
+# threads), 256 (64 lanes), 1024 (256 lanes: one row per block), 1028 (257 lanes: a second column trip)
+_EDGE_C = [1, 4, 20, 252, 256, 257, 1024, 1028]
+
+
+@pytest.mark.parametrize("B,N,P,C,kmax", [(16, 2048, 16, 512, 4), (3, 700, 16, 6, 16), (2, 5, 8, 3, 8)]
+                         + [(3, 257, 16, C, 16) for C in _EDGE_C] + [(2, 5, 8, C, 8) for C in _EDGE_C])
 def test_part_rows_matches_separate_ops(dev, B, N, P, C, kmax):
     """PartRowsFn (gather by part label + per-part sums, one-pass HIP backward) vs the separate
     ops it replaces (permute_rows + segment_sum, autograd's index_select / add / gather):
@@ -117,7 +142,8 @@ def test_part_rows_matches_separate_ops(dev, B, N, P, C, kmax):
         assert torch.equal(a.grad, b.grad), (a.grad - b.grad).abs().max().item()
 
 
-@pytest.mark.parametrize("B,N,P,C,kmax", [(16, 2048, 16, 512, 4), (3, 700, 16, 6, 16)])
+@pytest.mark.parametrize("B,N,P,C,kmax", [(16, 2048, 16, 512, 4), (3, 700, 16, 6, 16), (3, 257, 16, 20, 16),
+                                          (3, 257, 16, 1028, 16), (2, 5, 8, 20, 8), (2, 5, 8, 1028, 8)])
 def test_part_rows_alias_gradient(dev, B, N, P, C, kmax):
     """part_rows(alias=True): the third output is x itself (same values, same storage) and the
     gradient reaching it is added inside the regrouping's backward pass — equal, bitwise, to
@@ -144,6 +170,53 @@ def test_part_rows_alias_gradient(dev, B, N, P, C, kmax):
     xs4, sums4 = part_rows(d, parts)
     torch.autograd.backward([xs4, sums4], [gs, gp])
     assert torch.equal(c.grad, d.grad)
+
+
+def _rows_bwd_case(dev, C, seed):
+    """Inputs of ured_part_rows_bwd_add at (B, N, P) = (3, 257, 16) and the sum it must return,
+    (d_sorted[s] + d_sums[gid[s]]) + add with s the sorted position of each row, by torch ops."""
+    from ured_hip.ops import build_parts
+    B, N, P = 3, 257, 16
+    g = torch.Generator().manual_seed(seed)
+    labels = torch.randint(0, P, (B, N), generator=g).to(dev)
+    parts = build_parts(labels, torch.randn(B, N, 3, generator=g).to(dev), P)
+    ds, dg = torch.randn(B * N, C, generator=g).to(dev), torch.randn(B * P, C, generator=g).to(dev)
+    add = torch.randn(B, N, C, generator=g).to(dev)
+    s = (parts.inv_perm + torch.arange(B, device=dev).unsqueeze(1) * N).reshape(-1)
+    exp = ((ds[s] + dg[parts.gid[s].long()]) + add.view(B * N, C)).view(B, N, C)
+
+    def call(ds_, add_, out_):
+        from ured_hip import _lib
+        _lib.call("ured_part_rows_bwd_add", _lib.ptr(ds_), _lib.ptr(dg), _lib.ptr(parts.inv_perm), _lib.ptr(parts.gid),
+                  B, N, C, _lib.ptr(add_), _lib.ptr(out_), _lib.stream_of(out_))
+        return out_
+    return ds, add, exp, call
+
+
+def test_part_rows_bwd_unaligned_takes_scalar_path(dev):
+    """C = 8 is a float4 width, but a d_sorted that starts one float into its storage is not 16-byte
+    aligned: the call takes the scalar kernel and returns the aligned call's bits."""
+    ds, add, exp, call = _rows_bwd_case(dev, 8, 31)
+    aligned = call(ds, add, torch.full_like(add, float("nan")))
+    buf = torch.empty(ds.numel() + 1, device=dev)
+    buf[1:].copy_(ds.reshape(-1))
+    ds_off = buf[1:].view(ds.shape)
+    assert ds_off.is_contiguous() and ds.data_ptr() % 16 == 0 and ds_off.data_ptr() % 16 == 4
+    unaligned = call(ds_off, add, torch.full_like(add, float("nan")))
+    assert torch.equal(unaligned, aligned)
+    assert torch.equal(aligned, exp)
+
+
+@pytest.mark.parametrize("C", [8, 6])
+def test_part_rows_bwd_add_in_place(dev, C):
+    """`add` may be `out` itself (include/ured_hip.h): accumulating in place returns the bits of the
+    call with a separate `add`, on the float4 (C = 8) and the scalar (C = 6) kernel."""
+    ds, add, exp, call = _rows_bwd_case(dev, C, 32 + C)
+    separate = call(ds, add, torch.full_like(add, float("nan")))
+    inplace = add.clone()
+    call(ds, inplace, inplace)
+    assert torch.equal(inplace, separate)
+    assert torch.equal(separate, exp)
 
 
 @pytest.mark.parametrize("B,N,P,gaps", [(3, 257, 16, True), (16, 2048, 16, False), (2, 5000, 32, True), (1, 7, 16, True)])
