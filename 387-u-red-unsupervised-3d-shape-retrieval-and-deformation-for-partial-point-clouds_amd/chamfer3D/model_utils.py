@@ -1,6 +1,8 @@
 """Drop-in for calc_cd / calc_dcd / calc_emd / fscore (Density_aware_Chamfer_Distance/utils_v2/model_utils.py:13-76,
 utils_v2/metrics/CD/fscore.py) on the HIP nearest-neighbour kernels, and gen_grid_up
-(Density_aware_Chamfer_Distance/utils/model_utils.py:251-264).
+(Density_aware_Chamfer_Distance/utils/model_utils.py:251-264), and the geometric helpers of VRCNet's encoder
+(knn, knn_point, get_edge_features, edge_preserve_sampling, three_nn_upsampling; utils/model_utils.py:200-236,
+353-370, 397-404) on the HIP search, sampling and pooling kernels.
 
 Note the reference's argument order: calc_cd(output, gt) evaluates cham_loss(gt, output), so
 dist1 is gt -> output (model_utils.py:56); kept here.
@@ -104,3 +106,75 @@ def calc_emd(output, gt, eps=0.005, iterations=50):
     from emd import emd
     dist, _ = emd()(output, gt, eps, iterations)
     return torch.sqrt(dist).mean(1), dist
+
+
+# ---------------- VRCNet encoder helpers (utils/model_utils.py:200-236, 353-370, 397-404) ----------------
+
+def knn(x, k):
+    """x [B, D, N] -> int64 [B, N, k]: the k points of the same cloud nearest to each point, the point
+    itself included, ranked by (direct squared distance, index). D = 3 goes through ured_hip.nn.knn,
+    any other D through ured_hip.vn.knn_rows. No gradient."""
+    if x.dim() != 3:
+        raise ValueError(f"knn: x must be [B, D, N], got {tuple(x.shape)}")
+    rows = x.detach().transpose(1, 2).contiguous().float()
+    if k > rows.shape[1]:
+        raise ValueError(f"knn: k {k} exceeds the cloud's {rows.shape[1]} points")
+    if rows.shape[2] == 3:
+        return unn.knn(rows, rows, k)[1].long()
+    from ured_hip import vn
+    return vn.knn_rows(rows, k).long()
+
+
+def knn_point(pk, point_input, point_output):
+    """The pk points of point_input [B, N, 3] nearest to each point of point_output [B, M, 3] ->
+    (dist [B, M, pk] the negated squared distance, descending; idx int64 [B, M, pk]), as the
+    reference's topk of -d^2. Ties go to the lowest index."""
+    if pk > point_input.shape[1]:
+        raise ValueError(f"knn_point: pk {pk} exceeds the cloud's {point_input.shape[1]} points")
+    d, idx = unn.knn(point_output.detach().float().contiguous(), point_input.detach().float().contiguous(), pk)
+    return -d, idx.long()
+
+
+def get_edge_features(x, idx):
+    """x [B, C, 1, N], idx [B, N, k] -> [B, C, k, N], the gathered neighbour features. Kept for parity
+    with the reference's interface; the modules of models/vrcnet.py never build this tensor."""
+    B, N, k = idx.shape
+    rows = x.squeeze(2).transpose(2, 1).contiguous().view(B * N, -1)
+    flat = (idx.long() + torch.arange(B, device=idx.device).view(-1, 1, 1) * N).view(-1)
+    return rows[flat].view(B, N, k, -1).permute(0, 3, 2, 1)
+
+
+def edge_preserve_sampling_rows(feat, point_input, num_samples, k=10):
+    """The point-major form the encoder uses. feat [B, N, C], point_input [B, N, 3] -> (rows [B*S, 2C], slot
+    uint8 [B, S, C], p_idx int32 [B, S], pn_idx int32 [B, S, pk], point_output [B, S, 3]), S = num_samples."""
+    from ured_hip import group
+    from ured_hip.vrc import EdgePoolFn
+    B, N, _ = feat.shape
+    pts = point_input.detach().float().contiguous()
+    p_idx = group.fps(pts, num_samples, start=torch.zeros(B, dtype=torch.int32, device=pts.device))
+    point_output = torch.gather(point_input, 1, p_idx.long().unsqueeze(-1).expand(-1, -1, 3)).contiguous()
+    pn_idx = knn_point(int(min(k, N)), point_input, point_output)[1].int()
+    rows, slot = EdgePoolFn.apply(feat, p_idx, pn_idx)
+    return rows, slot, p_idx, pn_idx, point_output
+
+
+def edge_preserve_sampling(feature_input, point_input, num_samples, k=10):
+    """feature_input [B, C, N], point_input [B, N, 3] -> (net [B, 2C, num_samples], p_idx int32
+    [B, num_samples], pn_idx int32 [B, num_samples, pk], point_output [B, num_samples, 3]): farthest-point
+    sampling from index 0, the pk = min(k, N) nearest input points of every sample, and the sample's own
+    feature over the channel-wise max of its neighbours' (ured_hip.vrc.EdgePoolFn)."""
+    B, C, N = feature_input.shape
+    out, _, p_idx, pn_idx, point_output = edge_preserve_sampling_rows(feature_input.transpose(1, 2).contiguous(), point_input,
+                                                                      num_samples, k)
+    return out.view(B, num_samples, 2 * C).transpose(1, 2), p_idx, pn_idx, point_output
+
+
+def three_nn_upsampling(target_points, source_points):
+    """target [B, N, 3], source [B, S, 3] -> (idx int32 [B, N, K], weight [B, N, K]), K = min(3, S): the K
+    nearest source points of every target point in (distance, index) order and
+    weight = (1 / dist) / sum(1 / dist) with dist = max(sqrt(d^2), 1e-10). No gradient."""
+    K_ = min(3, source_points.shape[1])
+    d2, idx = unn.knn(target_points.detach().float().contiguous(), source_points.detach().float().contiguous(), K_)
+    dist = torch.sqrt(d2).clamp(min=1e-10)
+    inv = 1.0 / dist
+    return idx, inv / inv.sum(2, keepdim=True)

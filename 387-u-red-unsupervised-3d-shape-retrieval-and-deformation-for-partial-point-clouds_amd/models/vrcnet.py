@@ -1,0 +1,284 @@
+"""VRCNet's self-attention encoder (Density_aware_Chamfer_Distance/models/vrcnet.py:15-290) on the HIP
+Functions of ured_hip.vrc: SA_module, SK_SA_module, SKN_Res_unit, SA_SKN_Res_encoder and Linear_ResBlock.
+
+Same names, constructor arguments, parameter names and shapes as the reference (the nn.Conv2d /
+nn.Linear modules only hold the parameters, Conv2d weights stay [out, in, 1, 1]), so a reference
+state_dict loads with strict=True. forward takes and returns the reference's layouts; forward_rows
+keeps everything point-major [B*N, C] between layers.
+
+What differs in how it is computed, not in what:
+  - conv1 / conv2 / conv3 of an SA_module commute with the neighbour gather, so they are one GEMM per
+    point on stacked weights and the attention core (SaFn) gathers projected rows; no [B, C, k, N]
+    tensor is built. The ReLU in front of them is the GEMM's prologue.
+  - conv1 and conv_res of an SKN_Res_unit read the same input: one GEMM on stacked weights.
+  - the global half of conv6 is a per-cloud row bias of the GEMM; the repeat is never built.
+  - each level's kNN and FPS run once and are shared by all branches.
+nn.Dropout stays torch's own. EF_expansion, Folding, MSAP_SKN_decoder and Model are not built.
+
+Setting `net.decisions = {}` on a module makes its next forward export the discrete decisions: the
+kNN / FPS / pooling-neighbour / three-NN indices of the encoder, the pre-activation of every ReLU
+('pre': name -> tensor, the mask is pre > 0) and the pool slots.
+"""
+import torch
+import torch.nn as nn
+
+from chamfer3D.model_utils import edge_preserve_sampling_rows, knn, three_nn_upsampling
+from ured_hip.vrc import (CMAX, MaxRowsFn, MMAX, ReluFn, SaFn, SkMeanFn, SkMixFn, UnpoolFn, linear_rows,
+                          sa_check)
+
+
+def _w2(conv):
+    return conv.weight.reshape(conv.weight.shape[0], -1)
+
+
+def _rows(x):
+    """[B, C, 1, N] or [B, C, N] -> point-major [B*N, C]."""
+    if x.dim() == 4:
+        x = x.squeeze(2)
+    return x.transpose(1, 2).reshape(-1, x.shape[1])
+
+
+def _unrows(y, B, N, four=True):
+    y = y.view(B, N, -1).transpose(1, 2)
+    return y.unsqueeze(2) if four else y
+
+
+def _note(rec, name, t):
+    if rec is not None:
+        rec.setdefault("pre", {})[name] = t
+
+
+class SA_module(nn.Module):
+    def __init__(self, in_planes, rel_planes, mid_planes, out_planes, share_planes=8, k=16):
+        super().__init__()
+        if mid_planes % share_planes:
+            raise ValueError(f"SA_module: share_planes {share_planes} must divide mid_planes {mid_planes}")
+        if in_planes > CMAX:
+            raise ValueError(f"SA_module: in_planes {in_planes} exceeds {CMAX}")
+        sa_check("SA_module", 1, k, k, rel_planes, mid_planes, share_planes)
+        self.share_planes = share_planes
+        self.k = k
+        self.conv1 = nn.Conv2d(in_planes, rel_planes, kernel_size=1)
+        self.conv2 = nn.Conv2d(in_planes, rel_planes, kernel_size=1)
+        self.conv3 = nn.Conv2d(in_planes, mid_planes, kernel_size=1)
+        self.conv_w = nn.Sequential(nn.ReLU(inplace=False),
+                                    nn.Conv2d(rel_planes * (k + 1), mid_planes // share_planes, kernel_size=1, bias=False),
+                                    nn.ReLU(inplace=False),
+                                    nn.Conv2d(mid_planes // share_planes, k * mid_planes // share_planes, kernel_size=1))
+        self.activation_fn = nn.ReLU(inplace=False)
+        self.conv_out = nn.Conv2d(mid_planes, out_planes, kernel_size=1)
+
+    def forward_rows(self, x, idx, rec=None, tag="sa"):
+        """x [B*N, C] (the pre-ReLU input), idx int32 [B, N, k] -> [B*N, out_planes]."""
+        if idx.dim() != 3 or idx.shape[2] != self.k:
+            raise ValueError(f"SA_module: idx must be [B, N, {self.k}], got {tuple(idx.shape)}")
+        if idx.dtype != torch.int32:
+            raise TypeError(f"SA_module: idx must be int32, got {idx.dtype}")
+        if self.k > idx.shape[1]:
+            raise ValueError(f"SA_module: k {self.k} exceeds the cloud's {idx.shape[1]} points")
+        rel, mid = self.conv1.out_channels, self.conv3.out_channels
+        W = torch.cat((_w2(self.conv1), _w2(self.conv2), _w2(self.conv3)), 0)
+        b = torch.cat((self.conv1.bias, self.conv2.bias, self.conv3.bias), 0)
+        P = linear_rows(x, W, b, relu_in=True)
+        got = {} if rec is not None else None
+        o = SaFn.apply(P, idx, _w2(self.conv_w[1]), _w2(self.conv_w[3]), self.conv_w[3].bias, rel, mid, self.share_planes,
+                       got)
+        if rec is not None:
+            _note(rec, tag + ".x", x)
+            _note(rec, tag + ".P", P)
+            _note(rec, tag + ".h", got["h"])
+            _note(rec, tag + ".o", got["o"])
+        return linear_rows(o, _w2(self.conv_out), self.conv_out.bias) + x
+
+    def forward(self, input):
+        x, idx = input
+        B, _, _, N = x.shape
+        rec = getattr(self, "decisions", None)
+        y = self.forward_rows(_rows(x), idx.int(), rec if isinstance(rec, dict) else None)
+        return [_unrows(y, B, N), idx]
+
+
+class Linear_ResBlock(nn.Module):
+    def __init__(self, input_size=1024, output_size=256):
+        super().__init__()
+        self.conv1 = nn.Linear(input_size, input_size)
+        self.conv2 = nn.Linear(input_size, output_size)
+        self.conv_res = nn.Linear(input_size, output_size)
+        self.af = nn.ReLU(inplace=False)
+
+    def forward(self, feature):
+        """conv2(relu(conv1(f))) + conv_res(f) with f = relu(feature): the reference's ReLU is in place, so
+        its conv_res reads the rectified input too. The caller's tensor is left as it is here."""
+        f = self.af(feature)
+        return self.conv2(self.af(self.conv1(f))) + self.conv_res(f)
+
+
+class SK_SA_module(nn.Module):
+    def __init__(self, in_planes, rel_planes, mid_planes, out_planes, share_planes=8, k=[10, 20], r=2, L=32):
+        super().__init__()
+        if not 1 <= len(k) <= MMAX:
+            raise ValueError(f"SK_SA_module: {len(k)} neighbourhood sizes, expected 1..{MMAX}")
+        self.num_kernels = len(k)
+        d = max(int(out_planes / r), L)
+        self.sams = nn.ModuleList([SA_module(in_planes, rel_planes, mid_planes, out_planes, share_planes, k[i])
+                                   for i in range(len(k))])
+        self.fc = nn.Linear(out_planes, d)
+        self.fcs = nn.ModuleList([nn.Linear(d, out_planes) for _ in range(len(k))])
+        self.softmax = nn.Softmax(dim=1)
+        self.af = nn.ReLU(inplace=False)
+
+    def forward_rows(self, x, idxs, B, relu_out=False, rec=None, tag="sk"):
+        """x [B*N, C], idxs: one int32 [B, N, k_i] per branch -> [B*N, out_planes]; relu_out applies the
+        ReLU that SKN_Res_unit puts right after the selection."""
+        assert self.num_kernels == len(idxs)
+        ys = [sam.forward_rows(x, idxs[i], rec, f"{tag}.sam{i}") for i, sam in enumerate(self.sams)]
+        for i, y in enumerate(ys):
+            _note(rec, f"{tag}.fea{i}", y)
+        s = SkMeanFn.apply(B, *ys)
+        z = self.fc(s)
+        a = self.softmax(torch.stack([fc(z) for fc in self.fcs], 1))
+        v = SkMixFn.apply(a, relu_out, *ys)
+        if relu_out:
+            _note(rec, f"{tag}.v", v)
+        return v
+
+    def forward(self, input):
+        x, idxs = input
+        B, _, _, N = x.shape
+        rec = getattr(self, "decisions", None)
+        v = self.forward_rows(_rows(x), [i.int() for i in idxs], B, False, rec if isinstance(rec, dict) else None)
+        return [_unrows(v, B, N), idxs]
+
+
+class SKN_Res_unit(nn.Module):
+    def __init__(self, input_size, output_size, k=[10, 20], layers=1):
+        super().__init__()
+        self.conv1 = nn.Conv2d(input_size, output_size, 1, bias=False)
+        self.sam = self._make_layer(output_size, output_size // 16, output_size // 4, output_size, int(layers), 8, k=k)
+        self.conv2 = nn.Conv2d(output_size, output_size, 1, bias=False)
+        self.conv_res = nn.Conv2d(input_size, output_size, 1, bias=False)
+        self.af = nn.ReLU(inplace=False)
+
+    def _make_layer(self, in_planes, rel_planes, mid_planes, out_planes, blocks, share_planes=8, k=16):
+        return nn.Sequential(*[SK_SA_module(in_planes, rel_planes, mid_planes, out_planes, share_planes, k)
+                               for _ in range(blocks)])
+
+    def forward_rows(self, feat, idxs, B, rec=None, tag="unit"):
+        """feat [B*N, C_in], idxs: one int32 [B, N, k_i] per branch -> [B*N, output_size]."""
+        Co = self.conv1.out_channels
+        Y = linear_rows(feat, torch.cat((_w2(self.conv1), _w2(self.conv_res)), 0))       # [conv1 | conv_res]
+        x, res = Y[:, :Co], Y[:, Co:]
+        n = len(self.sam)
+        for i, sk in enumerate(self.sam):
+            x = sk.forward_rows(x, idxs, B, i == n - 1, rec, f"{tag}.sk{i}")
+        if n == 0:
+            _note(rec, f"{tag}.x", x)
+            x = ReluFn.apply(x)
+        return linear_rows(x, _w2(self.conv2)) + res
+
+    def forward(self, feat, idx):
+        B, _, _, N = feat.shape
+        rec = getattr(self, "decisions", None)
+        y = self.forward_rows(_rows(feat), [i.int() for i in idx], B, rec if isinstance(rec, dict) else None)
+        return _unrows(y, B, N)
+
+
+class SA_SKN_Res_encoder(nn.Module):
+    def __init__(self, input_size=3, k=[10, 20], pk=16, output_size=64, layers=[2, 2, 2, 2],
+                 pts_num=[3072, 1536, 768, 384]):
+        super().__init__()
+        self.init_channel = 64
+        c1 = self.init_channel
+        self.sam_res1 = SKN_Res_unit(input_size, c1, k, int(layers[0]))
+        c2 = c1 * 2
+        self.sam_res2 = SKN_Res_unit(c2, c2, k, int(layers[1]))
+        c3 = c2 * 2
+        self.sam_res3 = SKN_Res_unit(c3, c3, k, int(layers[2]))
+        c4 = c3 * 2
+        self.sam_res4 = SKN_Res_unit(c4, c4, k, int(layers[3]))
+        self.conv5 = nn.Conv2d(c4, 1024, 1)
+        self.fc1 = nn.Linear(1024, 512)
+        self.fc2 = nn.Linear(512, 1024)
+        self.conv6 = nn.Conv2d(c4 + 1024, c4, 1)
+        self.conv7 = nn.Conv2d(c3 + c4, c3, 1)
+        self.conv8 = nn.Conv2d(c2 + c3, c2, 1)
+        self.conv9 = nn.Conv2d(c1 + c2, c1, 1)
+        self.conv_out = nn.Conv2d(c1, output_size, 1)
+        self.dropout = nn.Dropout()
+        self.af = nn.ReLU(inplace=False)
+        self.k = k
+        self.pk = pk
+        self.rate = 2
+        self.pts_num = pts_num
+
+    def _knns(self, pts, rec):
+        """pts [B, N, 3] -> one int32 [B, N, k_i] per neighbourhood size."""
+        out = [knn(pts.transpose(1, 2), ki).int() for ki in self.k]
+        if rec is not None:
+            rec.setdefault("knn", []).append(out)
+        return out
+
+    def _pool(self, x, pts, S, rec):
+        """x [B*N, C] (after the ReLU), pts [B, N, 3] -> (rows [B*S, 2C], the S sampled points)."""
+        B, N, _ = pts.shape
+        rows, slot, p_idx, pn_idx, out_pts = edge_preserve_sampling_rows(x.view(B, N, -1), pts, S, self.pk)
+        if rec is not None:
+            rec.setdefault("fps", []).append(p_idx)
+            rec.setdefault("pn_idx", []).append(pn_idx)
+            rec.setdefault("slot", []).append(slot)
+        return rows, out_pts
+
+    def _unpool(self, x, src_pts, tgt_pts, skip, rec):
+        """x [B*S, D2] on src_pts, skip [B*N, D1] on tgt_pts -> [B*N, D2 + D1]."""
+        B, S, _ = src_pts.shape
+        N = tgt_pts.shape[1]
+        idx, weight = three_nn_upsampling(tgt_pts, src_pts)
+        if rec is not None:
+            rec.setdefault("three_nn", []).append(idx)
+        return UnpoolFn.apply(x.view(B, S, -1), idx, weight, skip.view(B, N, -1))
+
+    def forward_rows(self, features):
+        """features [B, C_in, N] (the first three channels are the coordinates) -> rows [B*N, output_size]."""
+        if features.dim() != 3 or features.shape[1] < 3:
+            raise ValueError(f"SA_SKN_Res_encoder: features must be [B, C >= 3, N], got {tuple(features.shape)}")
+        B, _, N = features.shape
+        if N != self.pts_num[0]:
+            raise ValueError(f"SA_SKN_Res_encoder: {N} points, pts_num[0] is {self.pts_num[0]}")
+        rec = getattr(self, "decisions", None)
+        rec = rec if isinstance(rec, dict) else None
+        X = features.transpose(1, 2).contiguous().view(B * N, -1)
+        pts = [features[:, 0:3, :].detach().transpose(1, 2).contiguous()]
+        units = (self.sam_res1, self.sam_res2, self.sam_res3, self.sam_res4)
+        skips = []
+        x = X
+        for lv, unit in enumerate(units):
+            if lv:
+                x, p = self._pool(skips[-1], pts[-1], self.pts_num[lv], rec)
+                pts.append(p)
+            x = unit.forward_rows(x, self._knns(pts[lv], rec), B, rec, f"res{lv + 1}")
+            _note(rec, f"x{lv + 1}", x)
+            skips.append(ReluFn.apply(x))
+        x1, x2, x3, x4 = skips
+        n4 = self.pts_num[3]
+        y5 = linear_rows(x4, _w2(self.conv5), self.conv5.bias)
+        g, win = MaxRowsFn.apply(y5, n4)
+        if rec is not None:
+            rec["win"] = win
+        a1 = linear_rows(g, self.fc1.weight, self.fc1.bias)
+        _note(rec, "fc1", a1)
+        a2 = linear_rows(self.dropout(ReluFn.apply(a1)), self.fc2.weight, self.fc2.bias)
+        _note(rec, "fc2", a2)
+        g = self.dropout(ReluFn.apply(a2))
+        W6 = _w2(self.conv6)
+        R6 = linear_rows(g, W6[:, :1024])                      # the global half of conv6: a row bias per cloud
+        y = linear_rows(x4, W6[:, 1024:], self.conv6.bias, rowbias=R6, group_rows=n4)
+        _note(rec, "conv6", y)
+        for name, conv, lv, skip in (("conv7", self.conv7, 2, x3), ("conv8", self.conv8, 1, x2), ("conv9", self.conv9, 0, x1)):
+            u = self._unpool(ReluFn.apply(y), pts[lv + 1], pts[lv], skip, rec)
+            y = linear_rows(u, _w2(conv), conv.bias)
+            _note(rec, name, y)
+        return linear_rows(y, _w2(self.conv_out), self.conv_out.bias, relu_in=True)
+
+    def forward(self, features):
+        B, _, N = features.shape
+        return _unrows(self.forward_rows(features), B, N, four=False)

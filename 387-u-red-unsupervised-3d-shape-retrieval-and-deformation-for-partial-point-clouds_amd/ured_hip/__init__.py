@@ -17,6 +17,7 @@
   vn       Vector-Neuron DGCNN layers: knn_rows, VnEdgeFn, VnPointFn, VnMaxPoolFn, VnFrameFn, VnLinearFn
   dcd      density-aware chamfer as a training loss: DcdLossFn / dcd_loss (one launch each way after the NN)
   pcn      the PCN completion network: PcnEncoderFn, PcnDecoderFn and the fold / pool / ReLU kernels
+  vrc      VRCNet's self-attention encoder: SaFn, SkMeanFn, SkMixFn, EdgePoolFn, UnpoolFn, LinearRowsFn
   losshead the step's loss head (chamfer families, contrastive, residual, reconstruction, weighted sum)
 """
-from . import _lib, attn, dcd, gcn, group, interp, kernels, losshead, nn, node, occ, ops, optim, pcn, syncbn, vn  # noqa: F401
+from . import _lib, attn, dcd, gcn, group, interp, kernels, losshead, nn, node, occ, ops, optim, pcn, syncbn, vn, vrc  # noqa: F401

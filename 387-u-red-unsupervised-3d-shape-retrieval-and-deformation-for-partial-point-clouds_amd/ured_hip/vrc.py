@@ -1,0 +1,419 @@
+"""VRCNet's self-attention encoder (Density_aware_Chamfer_Distance/models/vrcnet.py:15-290) as autograd
+Functions on libured_hip.so: every matrix product is ured_gemm (ured_hip.kernels), the rest the kernels
+of csrc/vrc.hip. Activations are point-major [B*N][C] fp32; the contracts are written out in
+include/ured_hip.h.
+
+SaFn        the attention core of SA_module on the projected rows P = [x1 | x2p | x3p]: the 1x1
+            convolutions commute with the neighbour gather, so they run once per point (one GEMM) and
+            the kernel gathers rows; no [B, C, k, N] tensor exists. Saved for the backward: P, idx, o
+            and the per-point h [ms] and w [k ms].
+SkMeanFn    s[b][c] = mean over points of sum_i relu(y_i): the input of SK_SA_module's fc.
+SkMixFn     relu?(sum_i a[b][i][c] relu(y_i)): the selected feature.
+EdgePoolFn  centre row | max over the pk neighbour rows (lowest j on a tie), with the winning slot.
+UnpoolFn    three-point interpolation with given weights | skip features.
+LinearRowsFn / ReluFn / MaxRowsFn  the GEMM layers between them (bias, ReLU prologue, per-cloud row
+            bias), the ReLU and the max over a cloud's points.
+Arguments are validated before any device work; a tensor off the device raises (no CPU path).
+Backwards write every element, sum in a fixed ascending order and use no atomics. Caller's stream.
+"""
+import ctypes
+
+import torch
+from torch.autograd import Function
+
+from . import _lib
+from . import kernels as K
+from .pcn import _Relu, pool_bwd, relu
+
+_P, _I = ctypes.c_void_p, ctypes.c_int
+_lib.register({
+    "ured_vrc_sa_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "ured_vrc_sa_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
+    "ured_vrc_sk_mean_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
+    "ured_vrc_sk_mean_bwd": [_P, _P, _I, _I, _I, _P, _P],
+    "ured_vrc_sk_mix_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
+    "ured_vrc_sk_mix_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
+    "ured_vrc_pool_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
+    "ured_vrc_pool_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
+    "ured_vrc_unpool_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
+    "ured_vrc_unpool_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
+})
+
+KMAX, RELMAX, MIDMAX, MSMAX, MMAX, PKMAX = 32, 32, 128, 16, 4, 32      # URED_VRC_* (include/ured_hip.h)
+CMAX = 512                          # the widest SA_module input (the encoder's deepest level)
+MAX_B = 65535
+_LIM = 1 << 31
+WA_MIN_CHUNK, WA_CHUNKS = 32, 1024  # points per workgroup of the dWa partials: at least 32, about 1024 workgroups
+
+
+def _p(t):
+    return None if t is None else t.data_ptr()
+
+
+def _f32(who, name, t, shape):
+    if not torch.is_tensor(t) or t.dtype != torch.float32:
+        raise TypeError(f"{who}: {name} must be a float32 tensor")
+    if t.dim() != len(shape) or any(s is not None and s != d for s, d in zip(shape, t.shape)):
+        raise ValueError(f"{who}: {name} has shape {tuple(t.shape)}, expected {shape}")
+
+
+def _i32(who, name, t, shape):
+    if not torch.is_tensor(t) or t.dtype != torch.int32:
+        raise TypeError(f"{who}: {name} must be an int32 tensor, got {getattr(t, 'dtype', type(t))}")
+    if t.dim() != len(shape) or any(s is not None and s != d for s, d in zip(shape, t.shape)):
+        raise ValueError(f"{who}: {name} has shape {tuple(t.shape)}, expected {shape}")
+
+
+def sa_check(who, B, N, k, rel, mid, share_planes):
+    """The limits of the attention core -> ms."""
+    if not 1 <= k <= KMAX:
+        raise ValueError(f"{who}: k {k} outside [1, {KMAX}]")
+    if k > N:
+        raise ValueError(f"{who}: k {k} exceeds the cloud's {N} points")
+    if not 1 <= rel <= RELMAX or not 1 <= mid <= MIDMAX:
+        raise ValueError(f"{who}: rel {rel} outside [1, {RELMAX}] or mid {mid} outside [1, {MIDMAX}]")
+    if share_planes < 1 or mid % share_planes:
+        raise ValueError(f"{who}: share_planes {share_planes} must divide mid {mid}")
+    ms = mid // share_planes
+    if ms > MSMAX:
+        raise ValueError(f"{who}: mid / share_planes = {ms} exceeds {MSMAX}")
+    if B < 1 or B > MAX_B:
+        raise ValueError(f"{who}: B {B} outside [1, {MAX_B}]")
+    if B * N * max(2 * rel + mid, k * ms) >= _LIM or N * k >= _LIM:
+        raise ValueError(f"{who}: B * N * max(2 rel + mid, k ms) and N * k must stay below 2^31")
+    return ms
+
+
+class SaFn(Function):
+    """(P [B*N, 2 rel + mid], idx int32 [B,N,k], Wa [ms, rel (k+1)], Wb [k ms, ms], bb [k ms], rel, mid,
+    share_planes) -> o [B*N, mid]. record: optional dict that receives o, h and w."""
+
+    @staticmethod
+    def forward(ctx, P, idx, Wa, Wb, bb, rel, mid, share_planes, record=None):
+        who = "SaFn"
+        _i32(who, "idx", idx, (None, None, None))
+        B, N, k = idx.shape
+        rel, mid, share_planes = int(rel), int(mid), int(share_planes)
+        ms = sa_check(who, B, N, k, rel, mid, share_planes)
+        _f32(who, "P", P, (B * N, 2 * rel + mid))
+        _f32(who, "Wa", Wa, (ms, rel * (k + 1)))
+        _f32(who, "Wb", Wb, (k * ms, ms))
+        _f32(who, "bb", bb, (k * ms,))
+        _lib.require_device(P, idx, Wa, Wb, bb)
+        P, idx, Wa, Wb, bb = P.contiguous(), idx.contiguous(), Wa.contiguous(), Wb.contiguous(), bb.contiguous()
+        dev = P.device
+        o = torch.empty(B * N, mid, device=dev)
+        h = torch.empty(B * N, ms, device=dev)
+        w = torch.empty(B * N, k * ms, device=dev)
+        _lib.call("ured_vrc_sa_fwd", _p(P), _p(idx), _p(Wa), _p(Wb), _p(bb), B, N, k, rel, mid, ms, _p(o), _p(h), _p(w),
+                  _lib.stream_of(P))
+        if record is not None:
+            record.update(o=o, h=h, w=w)
+        ctx.save_for_backward(P, idx, Wa, Wb, o, h, w)
+        ctx.dims = (B, N, k, rel, mid, ms)
+        return o
+
+    @staticmethod
+    def backward(ctx, go):
+        P, idx, Wa, Wb, o, h, w = ctx.saved_tensors
+        B, N, k, rel, mid, ms = ctx.dims
+        BN, L, T = B * N, rel * (k + 1), k * ms
+        dev = P.device
+        go = go.contiguous()
+        chunk = max(WA_MIN_CHUNK, (BN + WA_CHUNKS - 1) // WA_CHUNKS)
+        nch = (BN + chunk - 1) // chunk
+        gm = torch.empty(BN, mid, device=dev)
+        dw = torch.empty(BN, T, device=dev)
+        dh = torch.empty(BN, ms, device=dev)
+        dP = torch.empty_like(P)
+        ws = torch.empty(nch, ms * L, device=dev)
+        _lib.call("ured_vrc_sa_bwd", _p(go), _p(o), _p(P), _p(idx), _p(Wa), _p(Wb), _p(h), _p(w), B, N, k, rel, mid, ms,
+                  chunk, _p(gm), _p(dw), _p(dh), _p(dP), _p(ws), _lib.stream_of(P))
+        dWa = K.colsum(ws).view(ms, L)
+        dWb = torch.empty(T, ms, device=dev)
+        K.wgrad(dw, T, h, ms, T, ms, BN, dWb, ms)
+        dbb = K.colsum(dw)
+        return dP, None, dWa, dWb, dbb, None, None, None, None
+
+
+def _branches(who, ys, B):
+    if not 1 <= len(ys) <= MMAX:
+        raise ValueError(f"{who}: {len(ys)} branches, expected 1..{MMAX}")
+    _f32(who, "y_0", ys[0], (None, None))
+    R, C = ys[0].shape
+    B = int(B)
+    if B < 1 or B > MAX_B or R % B or R < 1 or C < 1:
+        raise ValueError(f"{who}: {R} rows do not split into B = {B} clouds (1 <= B <= {MAX_B})")
+    for i, y in enumerate(ys):
+        _f32(who, f"y_{i}", y, (R, C))
+    if R * C >= _LIM:
+        raise ValueError(f"{who}: B * N * C must stay below 2^31")
+    return B, R // B, C
+
+
+def _four(ts):
+    return [_p(t) for t in ts] + [None] * (MMAX - len(ts))
+
+
+class SkMeanFn(Function):
+    """(B, y_0 .. y_{m-1} [B*N, C]) -> s [B, C] = mean over the cloud's points of sum_i relu(y_i)."""
+
+    @staticmethod
+    def forward(ctx, B, *ys):
+        who = "SkMeanFn"
+        B, N, C = _branches(who, ys, B)
+        _lib.require_device(*ys)
+        ys = [y.contiguous() for y in ys]
+        s = torch.empty(B, C, device=ys[0].device)
+        _lib.call("ured_vrc_sk_mean_fwd", *_four(ys), len(ys), B, N, C, _p(s), _lib.stream_of(s))
+        ctx.save_for_backward(*ys)
+        ctx.dims = (B, N, C)
+        return s
+
+    @staticmethod
+    def backward(ctx, ds):
+        ys = ctx.saved_tensors
+        B, N, C = ctx.dims
+        ds = ds.contiguous()
+        out = []
+        for i, y in enumerate(ys):
+            if not ctx.needs_input_grad[1 + i]:
+                out.append(None)
+                continue
+            dy = torch.empty_like(y)
+            _lib.call("ured_vrc_sk_mean_bwd", _p(y), _p(ds), B, N, C, _p(dy), _lib.stream_of(y))
+            out.append(dy)
+        return (None, *out)
+
+
+class SkMixFn(Function):
+    """(a [B, m, C], relu, y_0 .. y_{m-1} [B*N, C]) -> relu?(sum_i a[b][i][c] relu(y_i)) [B*N, C]."""
+
+    @staticmethod
+    def forward(ctx, a, relu_out, *ys):
+        who = "SkMixFn"
+        _f32(who, "a", a, (None, None, None))
+        B, N, C = _branches(who, ys, a.shape[0])
+        _f32(who, "a", a, (B, len(ys), C))
+        _lib.require_device(a, *ys)
+        a = a.contiguous()
+        ys = [y.contiguous() for y in ys]
+        out = torch.empty(B * N, C, device=a.device)
+        _lib.call("ured_vrc_sk_mix_fwd", *_four(ys), _p(a), len(ys), B, N, C, int(bool(relu_out)), _p(out),
+                  _lib.stream_of(out))
+        ctx.save_for_backward(a, out, *ys)
+        ctx.dims = (B, N, C, bool(relu_out))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        a, out, *ys = ctx.saved_tensors
+        B, N, C, relu_out = ctx.dims
+        g = g.contiguous()
+        dys = [torch.empty_like(y) for y in ys]
+        da = torch.empty_like(a)
+        _lib.call("ured_vrc_sk_mix_bwd", _p(g), _p(out), *_four(ys), _p(a), len(ys), B, N, C, int(relu_out), *_four(dys),
+                  _p(da), _lib.stream_of(g))
+        return (da, None, *dys)
+
+
+class EdgePoolFn(Function):
+    """(feat [B,N,C], p_idx int32 [B,S], pn_idx int32 [B,S,pk]) -> (out [B*S, 2C], slot uint8 [B,S,C]):
+    columns 0..C-1 the centre row feat[p_idx[s]], columns C..2C-1 max_j feat[pn_idx[s,j]] with the
+    lowest j on a tie, slot the winning j. The backward routes to the centre row and to the winning
+    neighbour only."""
+
+    @staticmethod
+    def forward(ctx, feat, p_idx, pn_idx):
+        who = "EdgePoolFn"
+        _f32(who, "feat", feat, (None, None, None))
+        B, N, C = feat.shape
+        _i32(who, "p_idx", p_idx, (B, None))
+        S = p_idx.shape[1]
+        _i32(who, "pn_idx", pn_idx, (B, S, None))
+        pk = pn_idx.shape[2]
+        if not 1 <= pk <= PKMAX:
+            raise ValueError(f"{who}: pk {pk} outside [1, {PKMAX}]")
+        if B < 1 or B > MAX_B or N < 1 or S < 1 or C < 1:
+            raise ValueError(f"{who}: bad sizes B={B} N={N} S={S} C={C}")
+        if B * N * C >= _LIM or 2 * B * S * C >= _LIM or B * S * pk >= _LIM:
+            raise ValueError(f"{who}: B * N * C, 2 * B * S * C and B * S * pk must stay below 2^31")
+        _lib.require_device(feat, p_idx, pn_idx)
+        feat, p_idx, pn_idx = feat.contiguous(), p_idx.contiguous(), pn_idx.contiguous()
+        out = torch.empty(B * S, 2 * C, device=feat.device)
+        slot = torch.empty(B, S, C, dtype=torch.uint8, device=feat.device)
+        _lib.call("ured_vrc_pool_fwd", _p(feat), _p(p_idx), _p(pn_idx), B, N, S, pk, C, _p(out), _p(slot),
+                  _lib.stream_of(feat))
+        ctx.save_for_backward(p_idx, pn_idx, slot)
+        ctx.dims = (B, N, S, pk, C)
+        ctx.mark_non_differentiable(slot)
+        return out, slot
+
+    @staticmethod
+    def backward(ctx, g, _gs):
+        p_idx, pn_idx, slot = ctx.saved_tensors
+        B, N, S, pk, C = ctx.dims
+        g = g.contiguous()
+        dfeat = torch.empty(B, N, C, device=g.device)
+        _lib.call("ured_vrc_pool_bwd", _p(g), _p(p_idx), _p(pn_idx), _p(slot), B, N, S, pk, C, _p(dfeat), _lib.stream_of(g))
+        return dfeat, None, None
+
+
+class UnpoolFn(Function):
+    """(feat2 [B,S,D2], idx int32 [B,N,K], weight [B,N,K], skip [B,N,D1] | None), K <= 3 -> [B*N, D2 + D1]:
+    sum_q weight[n][q] feat2[idx[n][q]] in columns 0..D2-1, the skip features after them (the column
+    order of the reference's torch.cat([x, x_skip], 1)). Gradients go to feat2 and skip only."""
+
+    @staticmethod
+    def forward(ctx, feat2, idx, weight, skip):
+        who = "UnpoolFn"
+        _f32(who, "feat2", feat2, (None, None, None))
+        B, S, D2 = feat2.shape
+        _i32(who, "idx", idx, (B, None, None))
+        N, Kq = idx.shape[1], idx.shape[2]
+        if not 1 <= Kq <= 3:
+            raise ValueError(f"{who}: K {Kq} outside [1, 3]")
+        _f32(who, "weight", weight, (B, N, Kq))
+        D1 = 0
+        if skip is not None:
+            _f32(who, "skip", skip, (B, N, None))
+            D1 = skip.shape[2]
+            if D1 < 1:
+                raise ValueError(f"{who}: skip has no channels")
+        if B < 1 or B > MAX_B or N < 1 or S < 1 or D2 < 1:
+            raise ValueError(f"{who}: bad sizes B={B} N={N} S={S} D2={D2}")
+        if B * N * (D2 + D1) >= _LIM or B * S * D2 >= _LIM:
+            raise ValueError(f"{who}: B * N * (D2 + D1) and B * S * D2 must stay below 2^31")
+        _lib.require_device(feat2, idx, weight, skip)
+        feat2, idx, weight = feat2.contiguous(), idx.contiguous(), weight.detach().contiguous()
+        skip = None if skip is None else skip.contiguous()
+        out = torch.empty(B * N, D2 + D1, device=feat2.device)
+        _lib.call("ured_vrc_unpool_fwd", _p(feat2), _p(idx), _p(weight), _p(skip), B, N, S, Kq, D2, D1, _p(out),
+                  _lib.stream_of(out))
+        ctx.save_for_backward(idx, weight)
+        ctx.dims = (B, N, S, Kq, D2, D1)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        idx, weight = ctx.saved_tensors
+        B, N, S, Kq, D2, D1 = ctx.dims
+        g = g.contiguous()
+        d2 = torch.empty(B, S, D2, device=g.device)
+        ds = torch.empty(B, N, D1, device=g.device) if D1 else None
+        _lib.call("ured_vrc_unpool_bwd", _p(g), _p(idx), _p(weight), B, N, S, Kq, D2, D1, _p(d2), _p(ds), _lib.stream_of(g))
+        return d2, None, None, ds
+
+
+class ReluFn(Function):
+    """max(x, 0) by ured_pcn_relu; the backward passes g where the output is positive."""
+
+    @staticmethod
+    def forward(ctx, x):
+        _lib.require_device(x)
+        out = relu(x.contiguous())
+        ctx.save_for_backward(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        out, = ctx.saved_tensors
+        return relu(out, g.contiguous())
+
+
+class LinearRowsFn(Function):
+    """y [M, Co] = act(x [M, Ci]) @ W [Co, Ci]^T (+ b) (+ rowbias[row // group_rows]); act = ReLU when
+    relu_in (the GEMM's A prologue), else the identity. x may be a column slice of a wider row-major
+    matrix (its row stride is the GEMM's lda)."""
+
+    @staticmethod
+    def forward(ctx, x, W, b, relu_in, rowbias, group_rows):
+        who = "LinearRowsFn"
+        _f32(who, "x", x, (None, None))
+        M, Ci = x.shape
+        _f32(who, "W", W, (None, Ci))
+        Co = W.shape[0]
+        if b is not None:
+            _f32(who, "b", b, (Co,))
+        if rowbias is not None:
+            _f32(who, "rowbias", rowbias, (None, Co))
+            if group_rows < 1 or rowbias.shape[0] * group_rows != M:
+                raise ValueError(f"{who}: rowbias {tuple(rowbias.shape)} x group_rows {group_rows} does not cover {M} rows")
+        if M < 1 or M * max(Ci, Co) >= _LIM:
+            raise ValueError(f"{who}: M {M} must be at least 1 and M * channels below 2^31")
+        _lib.require_device(x, W, b, rowbias)
+        if x.stride(1) != 1 or x.stride(0) < Ci:
+            x = x.contiguous()
+        W = W.contiguous()
+        b = None if b is None else b.contiguous()
+        dev = x.device
+        rl = _Relu(Ci, dev) if relu_in else None
+        y = torch.empty(M, Co, device=dev)
+        kw = {} if rl is None else rl.kw(Ci)
+        if rowbias is not None:
+            rowbias = rowbias.contiguous()
+            sws = torch.empty(K.nblocks(M), 2, Co, device=dev)      # the epilogue's statistics partials: unused
+            K.gemm(M, Co, Ci, x, x.stride(0), W, Ci, y, Co, bias=b, epi=K.EPI_FWD, stat_ws=sws, rowbias=rowbias, ldr=Co,
+                   group_rows=int(group_rows), **kw)
+        else:
+            K.gemm(M, Co, Ci, x, x.stride(0), W, Ci, y, Co, bias=b, **kw)
+        ctx.save_for_backward(x, W)
+        ctx.cfg = (bool(relu_in), b is not None, rowbias is not None, int(group_rows) if rowbias is not None else 0)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, W = ctx.saved_tensors
+        relu_in, has_b, has_rb, group_rows = ctx.cfg
+        need = ctx.needs_input_grad
+        M, Ci = x.shape
+        Co = W.shape[0]
+        dev = g.device
+        g = g.contiguous()
+        dx = dW = db = drb = None
+        if need[0]:
+            dx = torch.empty(M, Ci, device=dev)
+            K.gemm(M, Ci, Co, g, Co, W, Ci, dx, Ci, b_kmajor=True)
+            if relu_in:
+                dx = relu(x.contiguous(), dx)
+        if need[1]:
+            dW = torch.empty(Co, Ci, device=dev)
+            kw = {}
+            if relu_in:
+                rl = _Relu(Ci, dev)
+                kw = {"pro": K.PRO_ENC, "pro_s": rl.s, "pro_t": rl.t}
+            K.wgrad(g, Co, x, x.stride(0), Co, Ci, M, dW, Ci, **kw)
+        if has_b and need[2]:
+            db = K.colsum(g)
+        if has_rb and need[4]:
+            drb = K.group_colsum(g, Co, M // group_rows, group_rows=group_rows)
+        return dx, dW, db, None, drb, None
+
+
+def linear_rows(x, W, b=None, relu_in=False, rowbias=None, group_rows=0):
+    return LinearRowsFn.apply(x, W, b, relu_in, rowbias, group_rows)
+
+
+class MaxRowsFn(Function):
+    """x [B*N, C] -> (max over each cloud's N rows [B, C], the winning row of the [B*N] matrix int32
+    [B, C], the lowest on a tie); the winner alone takes the gradient."""
+
+    @staticmethod
+    def forward(ctx, x, N):
+        _f32("MaxRowsFn", "x", x, (None, None))
+        if N < 1 or x.shape[0] % N:
+            raise ValueError(f"MaxRowsFn: {x.shape[0]} rows do not split into clouds of {N}")
+        _lib.require_device(x)
+        x = x.contiguous()
+        C = x.shape[1]
+        rl = _Relu(C, x.device)
+        out, win = K.pool_rows(x, int(N), rl.s, rl.t, relu=False)
+        ctx.save_for_backward(win)
+        ctx.N = int(N)
+        ctx.mark_non_differentiable(win)
+        return out, win
+
+    @staticmethod
+    def backward(ctx, g, _gw):
+        win, = ctx.saved_tensors
+        return pool_bwd(g.contiguous(), win, ctx.N), None

@@ -46,6 +46,11 @@
  *   ured_pcn_relu / ured_pcn_pool_bwd / ured_pcn_fold_fwd / ured_pcn_fold_bwd / ured_pcn_center_fwd /
  *   ured_pcn_center_bwd <- the ReLUs, max-pools, concatenations and the `+ center` of PCN_encoder /
  *                       PCN_decoder (Density_aware_Chamfer_Distance/models/pcn.py:13-71) and their autograd.
+ *   ured_vrc_sa_fwd / ured_vrc_sa_bwd / ured_vrc_sk_mean_fwd / ured_vrc_sk_mean_bwd / ured_vrc_sk_mix_fwd /
+ *   ured_vrc_sk_mix_bwd / ured_vrc_pool_fwd / ured_vrc_pool_bwd / ured_vrc_unpool_fwd / ured_vrc_unpool_bwd
+ *                       <- the attention core of SA_module, the branch selection of SK_SA_module,
+ *                       edge_preserve_sampling's gather + max and three_interpolate
+ *                       (Density_aware_Chamfer_Distance/models/vrcnet.py:15-290) and their autograd.
  */
 #ifndef URED_HIP_H
 #define URED_HIP_H
@@ -58,7 +63,7 @@ extern "C" {
 #define URED_EINVAL 1001
 
 /* Library identification: returns URED_ABI_VERSION. */
-#define URED_ABI_VERSION 16  /* 16: ured_dcd_loss_fwd / ured_dcd_loss_bwd, ured_pcn_relu / ured_pcn_pool_bwd / ured_pcn_fold_fwd / ured_pcn_fold_bwd / ured_pcn_center_fwd / ured_pcn_center_bwd; 15:ured_vn_parts / ured_vn_knn / ured_vn_act_fwd / ured_vn_act_bwd / ured_vn_maxpool_fwd / ured_vn_maxpool_bwd / ured_vn_frame_fwd / ured_vn_frame_bwd; 14: ured_gcn_dirs / ured_gcn_conv_fwd / ured_gcn_conv_bwd / ured_gcn_conv_bwd_parts / ured_gcn_pool_fwd / ured_gcn_pool_bwd; 13: ured_interp_fwd / ured_interp_bwd; 12: ured_fps / ured_ball_query / ured_group_fwd / ured_group_bwd; 11: ured_knn_fwd / ured_knn_bwd; 10: ured_occlude; 9: ured_attn_fwd_sets / ured_attn_bwd_sets, ured_get_shape_src_fwd / _bwd; 8: ured_nn_bwd_set; 7: ured_copy_batch; 6: ured_part_rows_bwd_add; 5: node BN SyncBN fields (stats_out/stats_in, sums_out/sums_in); ured_bn_stats et al. */
+#define URED_ABI_VERSION 17  /* 17: ured_vrc_sa_fwd / ured_vrc_sa_bwd / ured_vrc_sk_mean_fwd / ured_vrc_sk_mean_bwd / ured_vrc_sk_mix_fwd / ured_vrc_sk_mix_bwd / ured_vrc_pool_fwd / ured_vrc_pool_bwd / ured_vrc_unpool_fwd / ured_vrc_unpool_bwd; 16: ured_dcd_loss_fwd / ured_dcd_loss_bwd, ured_pcn_relu / ured_pcn_pool_bwd / ured_pcn_fold_fwd / ured_pcn_fold_bwd / ured_pcn_center_fwd / ured_pcn_center_bwd; 15:ured_vn_parts / ured_vn_knn / ured_vn_act_fwd / ured_vn_act_bwd / ured_vn_maxpool_fwd / ured_vn_maxpool_bwd / ured_vn_frame_fwd / ured_vn_frame_bwd; 14: ured_gcn_dirs / ured_gcn_conv_fwd / ured_gcn_conv_bwd / ured_gcn_conv_bwd_parts / ured_gcn_pool_fwd / ured_gcn_pool_bwd; 13: ured_interp_fwd / ured_interp_bwd; 12: ured_fps / ured_ball_query / ured_group_fwd / ured_group_bwd; 11: ured_knn_fwd / ured_knn_bwd; 10: ured_occlude; 9: ured_attn_fwd_sets / ured_attn_bwd_sets, ured_get_shape_src_fwd / _bwd; 8: ured_nn_bwd_set; 7: ured_copy_batch; 6: ured_part_rows_bwd_add; 5: node BN SyncBN fields (stats_out/stats_in, sums_out/sums_in); ured_bn_stats et al. */
 int ured_abi_version(void);
 /* Thread-local message for the last failing call on this thread ("" if none). */
 const char* ured_last_error(void);
@@ -788,6 +793,82 @@ int ured_pcn_fold_bwd(const float* dH, const float* Y, int B, int num_coarse, in
                       float* ws, void* stream);
 int ured_pcn_center_fwd(const float* y, const float* cp, int B, int num_coarse, int scale, float* out, void* stream);
 int ured_pcn_center_bwd(const float* dF, const float* add, int B, int num_coarse, int scale, float* out, void* stream);
+
+/* ---------------- VRCNet self-attention encoder (csrc/vrc.hip) ---------------- */
+/* The pieces of models/vrcnet.py:15-290 that are not GEMMs; activations point-major [B*N][C] fp32,
+ * products and adds rounded separately, sums in the stated order, no float atomics, every output
+ * element written. B <= 65535 and every element count below 2^31 throughout.
+ *
+ * ured_vrc_sa_fwd: the attention core of SA_module per point n of cloud b.
+ *   P [B*N][2 rel + mid] = [x1 | x2p | x3p] (the three 1x1 convolutions of max(x, 0), per point),
+ *   idx int32 [B][N][k] (rows of the same cloud; an index outside [0, N) reads as a zero row),
+ *   Wa [ms][rel (k+1)], Wb [k ms][ms], bb [k ms], ms = mid / share_planes.
+ *     u[i] = max(x1[n][i], 0) for i < rel; u[rel + r k + j] = max(x2p[idx[n][j]][r], 0)
+ *     h[s] = max(sum_i Wa[s][i] u[i], 0): 64 interleaved partial sums (i = l, l + 64, .. ascending),
+ *            combined by a butterfly over l (xor 32, 16, .., 1)
+ *     w[t] = (sum_s Wb[t][s] h[s], s ascending) + bb[t], read as w[s][j] = w[s k + j]
+ *     o[n][c] = max(sum_j w[c mod ms][j] x3p[idx[n][j]][c], 0), j ascending
+ *   Writes o [B*N][mid], h [B*N][ms], w [B*N][k ms].
+ *   Limits: 1 <= k <= min(32, N), rel <= 32, mid <= 128, ms <= 16, ms divides mid.
+ * ured_vrc_sa_bwd: with G = go where o > 0 else 0 (written to gm [B*N][mid]):
+ *   dw[n][s k + j] = sum over c = s, s + ms, .. of G[n][c] x3p[idx[n][j]][c]      (written, [B*N][k ms])
+ *   dh[n][s] = (sum_t Wb[t][s] dw[n][t], t ascending) where h[n][s] > 0 else 0     (written, [B*N][ms])
+ *   dP[n][r] = (sum_s Wa[s][r] dh[n][s]) where x1[n][r] > 0 else 0, r < rel
+ *   dP[m][rel + r] = (sum over the entries idx[n][j] = m, ascending (n, j), of
+ *                     sum_s Wa[s][rel + r k + j] dh[n][s]) where x2p[m][r] > 0 else 0
+ *   dP[m][2 rel + c] = sum over the entries idx[n][j] = m, ascending (n, j), of G[n][c] w[n][(c mod ms) k + j]
+ *   wa_ws[q][s][i] = sum over the points n of chunk q (n / chunk = q, ascending) of dh[n][s] u[n][i]
+ *                    ([ceil(B*N / chunk)][ms][rel (k+1)]; the caller sums the chunks).
+ *   Every element of dP is written; a point no row names gets 0; an index outside [0, N) takes no
+ *   gradient. dWb = dw^T h and dbb = column sums of dw are left to the GEMM library.
+ *
+ * ured_vrc_sk_mean_fwd: s[b][c] = (sum_n sum_i max(y_i[b][n][c], 0)) / N for the m <= 4 branches y_i
+ *   [B*N][C] (i ascending inside; 4 interleaved row sums n = g, g + 4, .. combined in ascending g).
+ * ured_vrc_sk_mean_bwd: dy[b][n][c] = ds[b][c] / N where y[b][n][c] > 0 else 0 (one branch per call).
+ * ured_vrc_sk_mix_fwd: out = sum_i a[b][i][c] max(y_i[b][n][c], 0) (i ascending), a [B][m][C]; relu != 0
+ *   applies max(., 0) after it.
+ * ured_vrc_sk_mix_bwd: G = g where (relu == 0 or out > 0) else 0; dy_i = a_i G where y_i > 0 else 0;
+ *   da[b][i][c] = sum_n G max(y_i, 0) in the order of ured_vrc_sk_mean_fwd. `out` may be null when relu == 0.
+ *
+ * ured_vrc_pool_fwd: edge-preserved pooling. feat [B][N][C], p_idx int32 [B][S], pn_idx int32 [B][S][pk]:
+ *   out[b*S + s][c] = feat[b][p_idx[b][s]][c]; out[b*S + s][C + c] = max_j feat[b][pn_idx[b][s][j]][c],
+ *   slot[b][s][c] = the winning j, the lowest on a tie. An index outside [0, N) reads as a zero row.
+ *   pk <= 32.
+ * ured_vrc_pool_bwd: dfeat[b][m][c] = sum over s with p_idx[b][s] = m (ascending s) of g[b*S + s][c], then
+ *   + sum over (s, j) with pn_idx[b][s][j] = m and slot[b][s][c] = j (ascending (s, j)) of g[b*S + s][C + c].
+ *
+ * ured_vrc_unpool_fwd: out[b*N + n][c] = ((w0 f0 + w1 f1) + w2 f2)[c] for c < D2, f_q = feat2[b][idx[b][n][q]],
+ *   w = weight[b][n][q] as given (K <= 3 columns); out[b*N + n][D2 + c] = skip[b*N + n][c] for c < D1
+ *   (skip null iff D1 = 0). The interpolation first, the skip features after it.
+ * ured_vrc_unpool_bwd: dfeat2[b][m][c] = sum over the entries idx[b][n][q] = m, ascending (n, q), of
+ *   weight[b][n][q] * g[b*N + n][c]; dskip = the last D1 columns of g. No gradient to idx or weight. */
+#define URED_VRC_KMAX 32
+#define URED_VRC_RELMAX 32
+#define URED_VRC_MIDMAX 128
+#define URED_VRC_MSMAX 16
+#define URED_VRC_MMAX 4
+#define URED_VRC_PKMAX 32
+int ured_vrc_sa_fwd(const float* P, const int* idx, const float* Wa, const float* Wb, const float* bb, int B, int N, int k,
+                    int rel, int mid, int ms, float* o, float* h, float* w, void* stream);
+int ured_vrc_sa_bwd(const float* go, const float* o, const float* P, const int* idx, const float* Wa, const float* Wb,
+                    const float* h, const float* w, int B, int N, int k, int rel, int mid, int ms, int chunk, float* gm,
+                    float* dw, float* dh, float* dP, float* wa_ws, void* stream);
+int ured_vrc_sk_mean_fwd(const float* y0, const float* y1, const float* y2, const float* y3, int m, int B, int N, int C,
+                         float* s, void* stream);
+int ured_vrc_sk_mean_bwd(const float* y, const float* ds, int B, int N, int C, float* dy, void* stream);
+int ured_vrc_sk_mix_fwd(const float* y0, const float* y1, const float* y2, const float* y3, const float* a, int m, int B, int N,
+                        int C, int relu, float* out, void* stream);
+int ured_vrc_sk_mix_bwd(const float* g, const float* out, const float* y0, const float* y1, const float* y2, const float* y3,
+                        const float* a, int m, int B, int N, int C, int relu, float* dy0, float* dy1, float* dy2, float* dy3,
+                        float* da, void* stream);
+int ured_vrc_pool_fwd(const float* feat, const int* p_idx, const int* pn_idx, int B, int N, int S, int pk, int C, float* out,
+                      unsigned char* slot, void* stream);
+int ured_vrc_pool_bwd(const float* g, const int* p_idx, const int* pn_idx, const unsigned char* slot, int B, int N, int S,
+                      int pk, int C, float* dfeat, void* stream);
+int ured_vrc_unpool_fwd(const float* feat2, const int* idx, const float* w, const float* skip, int B, int N, int S, int K,
+                        int D2, int D1, float* out, void* stream);
+int ured_vrc_unpool_bwd(const float* g, const int* idx, const float* w, int B, int N, int S, int K, int D2, int D1,
+                        float* dfeat2, float* dskip, void* stream);
 
 /* ---------------- loss head (csrc/loss.hip) ---------------- */
 /* compute_cm_loss of the deformed shape `out` [B,S,3] and of its mirror image (x -> -x,

@@ -1,0 +1,277 @@
+"""Micro-benchmark of VRCNet's self-attention encoder (ured_hip.vrc, models/vrcnet.py) against the torch
+composition of the reference's formulas, on the same GPU in the same run. The encoder leg also counts
+the first level's rows whose neighbour set differs between the two versions' searches.
+
+  python tools/vrc_bench.py [--batch 32] [--iters 3] [--rounds 5] [--out FILE.json] [--timeout 300]
+
+Shapes are those of cfgs/vrc_dcd.yaml: N 3072, k 16, pk 10, layers 1,1,1,1, 4 input channels, 32 clouds.
+Legs: one SA unit at the first level (C 64: rel 4, mid 16) forward + backward; one edge pool
+(3072 -> 1536 points, C 64) forward + backward; one unpool (1536 -> 3072 points, 128 interpolated + 64
+skip channels) forward + backward; the whole encoder forward + backward. The baselines, written out
+below: the gathered [B, C, k, N] tensor with conv2 / conv3 run on it, the attention weights repeated
+over share_planes, all kept by autograd; the gathered [B, C, S, pk] tensor and its max; three gathered
+rows times their weights; for the encoder those pieces with the module's own parameters, the
+[B, N, N] matrix -|a|^2 - |b|^2 + 2ab with topk for every neighbour search, and the project's FPS kernel
+in both versions (torch has none).
+
+Each leg runs in a child process of its own under a time limit (a leg that fails or runs out of
+time ends the run; nothing further is started on the device); at most 16 CPU threads. Per leg both
+versions are warmed up, then timed in alternating rounds of `iters` calls between two device
+events; the figure is the median round (min and max beside it). Peak memory is the
+torch.cuda.max_memory_allocated delta of one call of each version over what is allocated before
+it. Prints one JSON line.
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+N, KNN, PK, CIN = 3072, 16, 10, 4
+PTS = [3072, 1536, 768, 384]
+LEGS = ["SA unit fwd+bwd C64 k16", "edge pool fwd+bwd 3072->1536 C64 pk10", "unpool fwd+bwd 1536->3072 128+64",
+        "encoder fwd+bwd"]
+
+
+# ---------------- the torch baselines (the reference's layouts: [B, C, 1, N]) ----------------
+
+def gather_torch(x, idx):
+    """x [B, C, N], idx [B, M, k] -> [B, C, k, M]."""
+    Bn, C, _ = x.shape
+    _, M, k = idx.shape
+    flat = idx.reshape(Bn, 1, M * k).expand(-1, C, -1)
+    return x.gather(2, flat).view(Bn, C, M, k).permute(0, 1, 3, 2)
+
+
+def knn_torch(q, p, k):
+    """q [B, M, 3], p [B, N, 3] -> the k nearest p of every q by the expansion, [B, M, k]."""
+    import torch
+    inner = torch.bmm(q, p.transpose(1, 2))
+    return (2 * inner - (q * q).sum(-1).unsqueeze(2) - (p * p).sum(-1).unsqueeze(1)).topk(k, dim=-1)[1]
+
+
+def sa_torch(m, x, idx):
+    import torch
+    import torch.nn.functional as F
+    Bn, _, _, Nn = x.shape
+    xr = F.relu(x)
+    xn = gather_torch(xr.squeeze(2), idx)
+    x1 = F.conv2d(xr, m.conv1.weight, m.conv1.bias)
+    x2 = F.conv2d(xn, m.conv2.weight, m.conv2.bias).reshape(Bn, -1, 1, Nn)
+    x3 = F.conv2d(xn, m.conv3.weight, m.conv3.bias)
+    w = m.conv_w(torch.cat((x1, x2), 1)).view(Bn, -1, m.k, Nn).repeat(1, m.share_planes, 1, 1)
+    out = F.relu((w * x3).sum(2, keepdim=True))
+    return F.conv2d(out, m.conv_out.weight, m.conv_out.bias) + x
+
+
+def sk_torch(sk, x, idxs):
+    import torch
+    import torch.nn.functional as F
+    feas = torch.stack([F.relu(sa_torch(sam, x, idxs[i])) for i, sam in enumerate(sk.sams)], 1)
+    z = sk.fc(feas.sum(1).mean(-1).mean(-1))
+    a = torch.softmax(torch.stack([fc(z) for fc in sk.fcs], 1), 1)
+    return (feas * a.unsqueeze(-1).unsqueeze(-1)).sum(1)
+
+
+def unit_torch(u, feat, idxs):
+    import torch.nn.functional as F
+    x = F.conv2d(feat, u.conv1.weight)
+    for sk in u.sam:
+        x = sk_torch(sk, x, idxs)
+    return F.conv2d(F.relu(x), u.conv2.weight) + F.conv2d(feat, u.conv_res.weight)
+
+
+def pool_torch(feat, p_idx, pn_idx):
+    """feat [B, C, N] -> [B, 2C, S]."""
+    import torch
+    centre = feat.gather(2, p_idx.unsqueeze(1).expand(-1, feat.shape[1], -1))
+    return torch.cat((centre, gather_torch(feat, pn_idx).max(2)[0]), 1)
+
+
+def unpool_torch(feat2, idx, weight, skip):
+    """feat2 [B, D2, S], idx / weight [B, N, 3], skip [B, D1, N] -> [B, D2 + D1, N]."""
+    import torch
+    return torch.cat(((gather_torch(feat2, idx) * weight.transpose(1, 2).unsqueeze(1)).sum(2), skip), 1)
+
+
+def encoder_torch(net, feats):
+    import torch
+    import torch.nn.functional as F
+    from ured_hip import group
+    Bn = feats.shape[0]
+    pts = [feats[:, 0:3, :].detach().transpose(1, 2).contiguous()]
+    x = feats.unsqueeze(2)
+    skips = []
+    for lv, unit in enumerate((net.sam_res1, net.sam_res2, net.sam_res3, net.sam_res4)):
+        if lv:
+            src = pts[-1]
+            p_idx = group.fps(src, net.pts_num[lv], start=torch.zeros(Bn, dtype=torch.int32, device=src.device)).long()
+            out_pts = src.gather(1, p_idx.unsqueeze(-1).expand(-1, -1, 3))
+            x = pool_torch(skips[-1].squeeze(2), p_idx, knn_torch(out_pts, src, net.pk)).unsqueeze(2)
+            pts.append(out_pts)
+        x = unit_torch(unit, x, [knn_torch(pts[lv], pts[lv], k) for k in net.k])
+        skips.append(F.relu(x))
+    x1, x2, x3, x4 = skips
+    g = F.conv2d(x4, net.conv5.weight, net.conv5.bias).max(-1)[0].view(Bn, -1)
+    g = net.dropout(F.relu(net.fc2(net.dropout(F.relu(net.fc1(g))))))
+    y = F.conv2d(torch.cat((g.view(Bn, -1, 1, 1).expand(-1, -1, 1, net.pts_num[3]), x4), 1), net.conv6.weight, net.conv6.bias)
+    for conv, lv, skip in ((net.conv7, 2, x3), (net.conv8, 1, x2), (net.conv9, 0, x1)):
+        d, idx = torch.cdist(pts[lv], pts[lv + 1]).topk(3, dim=-1, largest=False)
+        inv = 1.0 / d.clamp(min=1e-10)
+        u = unpool_torch(F.relu(y).squeeze(2), idx, inv / inv.sum(2, keepdim=True), skip.squeeze(2)).unsqueeze(2)
+        y = F.conv2d(u, conv.weight, conv.bias)
+    return F.conv2d(F.relu(y), net.conv_out.weight, net.conv_out.bias).squeeze(2)
+
+
+# ---------------- timing ----------------
+
+def _round(fn, iters):
+    import torch
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters * 1e3      # us per call
+
+
+def measure(fns, iters, rounds, warm=2):
+    import torch
+    for fn in fns.values():
+        for _ in range(warm):
+            fn()
+    torch.cuda.synchronize()
+    out = {}
+    for k, fn in fns.items():                      # peak memory of one call
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        fn()
+        torch.cuda.synchronize()
+        out[k] = {"peak_mb": (torch.cuda.max_memory_allocated() - base) / 1e6}
+    times = {k: [] for k in fns}
+    for _ in range(rounds):                        # alternate the versions
+        for k, fn in fns.items():
+            times[k].append(_round(fn, iters))
+    for k, v in times.items():
+        out[k].update({"median_us": statistics.median(v), "min_us": min(v), "max_us": max(v)})
+    return out
+
+
+def run_leg(leg, B, iters, rounds):
+    import torch
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    sys.path.insert(0, ROOT)
+    import __graft_entry__ as ge
+    ge.add_pkg_path()
+    from chamfer3D.model_utils import knn, three_nn_upsampling
+    from models import vrcnet as M
+    from ured_hip import vrc as V
+    if not torch.cuda.is_available():
+        raise SystemExit("vrc_bench: no GPU (times are measured on the device only)")
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(0)
+    res = {"batch": B}
+    i = LEGS.index(leg)
+    pts = (torch.rand(B, N, 3, generator=g) * 2 - 1).to(dev)
+
+    def stepper(leaves, go):
+        def step(fwd):
+            for t in leaves:
+                t.grad = None
+            fwd().backward(go)
+        return step
+
+    if i == 0:
+        C = 64
+        mod = M.SA_module(C, C // 16, C // 4, C, 8, KNN).to(dev)
+        x = torch.randn(B, C, 1, N, generator=g).to(dev).requires_grad_(True)
+        idx = knn(pts.transpose(1, 2), KNN)
+        go = torch.randn(B, C, 1, N, generator=g).to(dev)
+        step = stepper(list(mod.parameters()) + [x], go)
+        with torch.no_grad():
+            res["max_abs_diff"] = float((mod([x, idx])[0] - sa_torch(mod, x, idx)).abs().max())
+        fns = {"hip": lambda: step(lambda: mod([x, idx])[0]), "torch": lambda: step(lambda: sa_torch(mod, x, idx))}
+    elif i == 1:
+        from ured_hip import group
+        C, S = 64, PTS[1]
+        feat = torch.randn(B, N, C, generator=g).to(dev).requires_grad_(True)
+        p_idx = group.fps(pts, S, start=torch.zeros(B, dtype=torch.int32, device=dev))
+        pn_idx = knn_torch(pts.gather(1, p_idx.long().unsqueeze(-1).expand(-1, -1, 3)), pts, PK).int()
+        go = torch.randn(B * S, 2 * C, generator=g).to(dev)
+        pl, nl = p_idx.long(), pn_idx.long()
+
+        def base():
+            return pool_torch(feat.transpose(1, 2), pl, nl).transpose(1, 2).reshape(B * S, 2 * C)
+        with torch.no_grad():
+            res["max_abs_diff"] = float((V.EdgePoolFn.apply(feat, p_idx, pn_idx)[0] - base()).abs().max())
+        step = stepper([feat], go)
+        fns = {"hip": lambda: step(lambda: V.EdgePoolFn.apply(feat, p_idx, pn_idx)[0]), "torch": lambda: step(base)}
+    elif i == 2:
+        S, D2, D1 = PTS[1], 128, 64
+        src = pts[:, :S].contiguous()
+        feat2 = torch.randn(B, S, D2, generator=g).to(dev).requires_grad_(True)
+        skip = torch.randn(B, N, D1, generator=g).to(dev).requires_grad_(True)
+        idx, w = three_nn_upsampling(pts, src)
+        il = idx.long()
+        go = torch.randn(B * N, D2 + D1, generator=g).to(dev)
+
+        def base():
+            return unpool_torch(feat2.transpose(1, 2), il, w, skip.transpose(1, 2)).transpose(1, 2).reshape(B * N, D2 + D1)
+        with torch.no_grad():
+            res["max_abs_diff"] = float((V.UnpoolFn.apply(feat2, idx, w, skip) - base()).abs().max())
+        step = stepper([feat2, skip], go)
+        fns = {"hip": lambda: step(lambda: V.UnpoolFn.apply(feat2, idx, w, skip)), "torch": lambda: step(base)}
+    else:
+        net = M.SA_SKN_Res_encoder(CIN, [KNN], PK, 64, [1, 1, 1, 1], PTS).to(dev).eval()
+        feats = torch.cat((pts.transpose(1, 2), torch.randn(B, CIN - 3, N, generator=g).to(dev)), 1).requires_grad_(True)
+        go = torch.randn(B, 64, N, generator=g).to(dev)
+        step = stepper(list(net.parameters()) + [feats], go)
+        with torch.no_grad():
+            res["max_abs_diff"] = float((net(feats) - encoder_torch(net, feats)).abs().max())
+            a, b = knn(pts.transpose(1, 2), KNN), knn_torch(pts, pts, KNN)      # the first level's two searches
+            res["level1_rows_with_other_neighbour_sets"] = int((a.sort(-1)[0] != b.sort(-1)[0]).any(-1).sum())
+            res["level1_rows"] = B * N
+        fns = {"hip": lambda: step(lambda: net(feats)), "torch": lambda: step(lambda: encoder_torch(net, feats))}
+    res.update(measure(fns, iters, rounds))
+    res["torch_over_hip"] = res["torch"]["median_us"] / res["hip"]["median_us"]
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--timeout", type=int, default=300, help="seconds per leg")
+    ap.add_argument("--leg", default=None, help="(internal) run this one leg and print its JSON")
+    a = ap.parse_args()
+    if a.leg is not None:
+        print(json.dumps(run_leg(a.leg, a.batch, a.iters, a.rounds)))
+        return
+    res = {"batch": a.batch, "iters": a.iters, "rounds": a.rounds, "legs": {}}
+    for leg in LEGS:      # one child per leg, each under its own time limit; the first failure ends the run
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", leg, "--batch", str(a.batch), "--iters",
+                            str(a.iters), "--rounds", str(a.rounds)], capture_output=True, text=True, timeout=a.timeout)
+        if r.returncode != 0:
+            raise SystemExit(f"vrc_bench: leg '{leg}' failed (exit {r.returncode})\n{r.stdout[-2000:]}{r.stderr[-2000:]}")
+        v = json.loads(r.stdout.strip().splitlines()[-1])
+        res["legs"][leg] = v
+        print(f"{leg}: hip {v['hip']['median_us']:.1f} us ({v['hip']['min_us']:.1f}-{v['hip']['max_us']:.1f}) "
+              f"{v['hip']['peak_mb']:.1f} MB  torch {v['torch']['median_us']:.1f} us ({v['torch']['min_us']:.1f}-"
+              f"{v['torch']['max_us']:.1f}) {v['torch']['peak_mb']:.1f} MB  torch/hip {v['torch_over_hip']:.2f}  "
+              f"max |diff| {v['max_abs_diff']:.2e}", flush=True)
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
