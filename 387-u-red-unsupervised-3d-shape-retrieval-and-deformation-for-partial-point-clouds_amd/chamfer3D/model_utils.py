@@ -2,7 +2,8 @@
 utils_v2/metrics/CD/fscore.py) on the HIP nearest-neighbour kernels, and gen_grid_up
 (Density_aware_Chamfer_Distance/utils/model_utils.py:251-264), and the geometric helpers of VRCNet's encoder
 (knn, knn_point, get_edge_features, edge_preserve_sampling, three_nn_upsampling; utils/model_utils.py:200-236,
-353-370, 397-404) on the HIP search, sampling and pooling kernels.
+353-370, 397-404) on the HIP search, sampling and pooling kernels, and the decoder's EF_expansion with
+get_graph_feature (utils/model_utils.py:137-166, 267-289) on the edge kernels of ured_hip.vrc.
 
 Note the reference's argument order: calc_cd(output, gt) evaluates cham_loss(gt, output), so
 dist1 is gt -> output (model_utils.py:56); kept here.
@@ -178,3 +179,95 @@ def three_nn_upsampling(target_points, source_points):
     dist = torch.sqrt(d2).clamp(min=1e-10)
     inv = 1.0 / dist
     return idx, inv / inv.sum(2, keepdim=True)
+
+
+# ---------------- VRCNet decoder: edge-feature expansion (utils/model_utils.py:137-166, 267-289) ----------------
+
+def get_graph_feature(x, k=20, minus_center=True):
+    """x [B, C, N] -> [B, 2C, N, k]: the point's own feature over its k nearest neighbours' in feature space
+    (minus the point's own when minus_center). Kept for parity with the reference's interface; EF_expansion
+    never builds this tensor."""
+    idx = knn(x, k)
+    B, C, N = x.shape
+    rows = x.transpose(2, 1).contiguous()
+    flat = (idx + torch.arange(B, device=idx.device).view(-1, 1, 1) * N).view(-1)
+    feature = rows.view(B * N, -1)[flat].view(B, N, k, C)
+    centre = rows.view(B, N, 1, C).expand(-1, -1, k, -1)
+    return torch.cat((centre, feature - centre if minus_center else feature), 3).permute(0, 3, 1, 2)
+
+
+class EF_expansion(torch.nn.Module):
+    """Edge-feature expansion: every point becomes step_ratio points. Same constructor, parameter names and
+    shapes as the reference (Conv2d weights [out, in, 1, 1]). With idx = knn(x, k) in feature space:
+        f1[n, j]  = conv1([x_n | x_idx[n, j]])
+        f2[n, j]  = relu(conv2(relu([f1[n, j] | x_n | x_idx[n, j]])))                    [O r]
+        out[n r + s] = max_j conv3(f2[n, j][s O : (s + 1) O])
+    The centre and neighbour columns of conv1 / conv2 commute with the gather: they are per-point GEMMs on
+    stacked weights, and only the O -> O r product of conv2 on relu(f1) and conv3 run per edge
+    (ured_hip.vrc.EfEdgeFn / EfMaxFn). forward takes [B, C, N] and returns [B, O, N r]; forward_rows is
+    point-major. Setting `decisions = {}` exports the kNN indices, the ReLU layers and the max slots."""
+
+    def __init__(self, input_size, output_size=64, step_ratio=2, k=4):
+        super().__init__()
+        from ured_hip.vrc import CMAX, KMAX, OMAX, RMAX
+        if not 1 <= input_size <= CMAX:
+            raise ValueError(f"EF_expansion: input_size {input_size} outside [1, {CMAX}]")
+        if not 1 <= output_size <= OMAX:
+            raise ValueError(f"EF_expansion: output_size {output_size} outside [1, {OMAX}]")
+        if not 1 <= step_ratio <= RMAX:
+            raise ValueError(f"EF_expansion: step_ratio {step_ratio} outside [1, {RMAX}]")
+        if not 1 <= k <= KMAX:
+            raise ValueError(f"EF_expansion: k {k} outside [1, {KMAX}]")
+        self.step_ratio = step_ratio
+        self.k = k
+        self.input_size = input_size
+        self.output_size = output_size
+        self.conv1 = torch.nn.Conv2d(input_size * 2, output_size, 1)
+        self.conv2 = torch.nn.Conv2d(input_size * 2 + output_size, output_size * step_ratio, 1)
+        self.conv3 = torch.nn.Conv2d(output_size, output_size, 1)
+
+    def core_rows(self, x, idx, rec=None, tag="ef"):
+        """x [B*N, C], idx int32 [B, N, k] (given) -> [B*N*r, O], row n r + s."""
+        from ured_hip.vrc import EfEdgeFn, EfMaxFn, linear_rows
+        C, O, r = self.input_size, self.output_size, self.step_ratio
+        if idx.dim() != 3 or idx.shape[2] != self.k:
+            raise ValueError(f"EF_expansion: idx must be [B, N, {self.k}], got {tuple(idx.shape)}")
+        if idx.dtype != torch.int32:
+            raise TypeError(f"EF_expansion: idx must be int32, got {idx.dtype}")
+        B, N, k = idx.shape
+        if x.dim() != 2 or x.shape[0] != B * N or x.shape[1] != C:
+            raise ValueError(f"EF_expansion: x must be [{B * N}, {C}], got {tuple(x.shape)}")
+        W1 = self.conv1.weight.view(O, 2 * C)
+        W2 = self.conv2.weight.view(O * r, O + 2 * C)
+        zero1, zero2 = torch.zeros_like(self.conv1.bias), torch.zeros_like(self.conv2.bias)
+        # [centre | neighbour] halves of conv1 on x and of conv2 on relu(x): one GEMM each, per point
+        P1 = linear_rows(x, torch.cat((W1[:, :C], W1[:, C:]), 0), torch.cat((self.conv1.bias, zero1), 0))
+        P2 = linear_rows(x, torch.cat((W2[:, O:O + C], W2[:, O + C:]), 0), torch.cat((self.conv2.bias, zero2), 0),
+                         relu_in=True)
+        got1, got2 = ({}, {}) if rec is not None else (None, None)
+        e1 = EfEdgeFn.apply(P1, idx, None, got1)                              # relu(f1) [B*N*k, O]
+        f2 = EfEdgeFn.apply(P2, idx, linear_rows(e1, W2[:, :O]), got2)        # [B*N*k, O r]
+        H = linear_rows(f2.view(B * N * k * r, O), self.conv3.weight.view(O, O), self.conv3.bias)
+        out, slot = EfMaxFn.apply(H, B, N, k, r)
+        if rec is not None:
+            pre = rec.setdefault("pre", {})
+            pre[tag + ".x"], pre[tag + ".f1"], pre[tag + ".f2"] = x, got1["out"], got2["out"]
+            rec.setdefault("slot", {})[tag] = slot
+            rec.setdefault("H", {})[tag] = H
+        return out
+
+    def forward_rows(self, x, B, rec=None, tag="ef"):
+        """x [B*N, C] -> [B*N*r, O]; the neighbours are found here, in feature space."""
+        if x.dim() != 2 or x.shape[0] % B:
+            raise ValueError(f"EF_expansion: {tuple(x.shape)} rows do not split into {B} clouds")
+        N = x.shape[0] // B
+        idx = knn(x.detach().reshape(B, N, -1).transpose(1, 2), self.k).int()
+        if rec is not None:
+            rec.setdefault("knn", {})[tag] = idx
+        return self.core_rows(x, idx, rec, tag)
+
+    def forward(self, x):
+        B, C, N = x.shape
+        rec = getattr(self, "decisions", None)
+        y = self.forward_rows(x.transpose(1, 2).reshape(B * N, C), B, rec if isinstance(rec, dict) else None)
+        return y.view(B, N * self.step_ratio, self.output_size).transpose(1, 2)

@@ -32,6 +32,12 @@
 //   dWb = dw^T h and dbb = colsum(dw) are the caller's GEMM and column sum.
 // ured_vrc_sk_mean_fwd / _bwd, ured_vrc_sk_mix_fwd / _bwd: see include/ured_hip.h.
 // ured_vrc_pool_fwd / _bwd, ured_vrc_unpool_fwd / _bwd: see include/ured_hip.h.
+// The decoder (EF_expansion of utils/model_utils.py:137-166, Folding of models/vrcnet.py:54-86):
+// ured_vrc_ef_edge_fwd / _bwd  per-edge rows max((G +) centre[n] + neighbour[idx[n][j]], 0) from per-point
+//   halves; the backward sums the centre half over j and scatters the neighbour half in the ordered
+//   scheme of ured_vrc_sa_bwd.
+// ured_vrc_ef_max_fwd / _bwd   the max over the k slots of conv3's rows, with the winning slot.
+// ured_vrc_fold_fwd / _bwd     max(U[n] + T[s], 0) over the r grid points of every coarse point.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #define URED_DBG_FILE 18
@@ -578,8 +584,190 @@ __global__ __launch_bounds__(VRC_T) void unpool_bwd_skip_kernel(const float* __r
     dskip[i] = g[r * (D2 + D1) + D2 + c];
 }
 
+// ---------------- EF expansion: edge rows, max over the k slots ----------------
+
+// out[(n k + j)][c] = max((G[(n k + j)][c] + P[n][c]) + P[idx[n][j]][W + c], 0), P [B*N][2 W] = [centre | neighbour];
+// without G the first add drops out. An index outside [0, N) reads as a zero neighbour row.
+__global__ __launch_bounds__(VRC_T) void ef_edge_fwd_kernel(const float* __restrict__ G, const float* __restrict__ P,
+                                                            const int* __restrict__ idx, int N, int k, int W,
+                                                            long long total, float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * VRC_T + threadIdx.x;
+    if (i >= total) return;                           // total = B * N * k * W
+    const long long e = i / W;                        // (b N + n) k + j
+    const int c = (int)(i - e * W);
+    const long long rn = e / k;
+    const long long b = rn / N;
+    const int id = idx[e];
+    URED_DBG_CHECK((b + 1) * N * k * W <= total);
+    float v = P[rn * 2 * W + c];
+    if (G) v = G[i] + v;
+    if (id >= 0 && id < N) v += P[(b * N + id) * 2 * W + W + c];
+    out[i] = fmaxf(v, 0.f);
+}
+
+// With M = g where out > 0 else 0: dG = M (when asked for); dP[n][c] = sum_j M[(n k + j)][c], j ascending.
+__global__ __launch_bounds__(VRC_T) void ef_edge_bwd_point_kernel(const float* __restrict__ g, const float* __restrict__ out,
+                                                                  int k, int W, long long total, float* __restrict__ dG,
+                                                                  float* __restrict__ dP) {
+    const long long i = (long long)blockIdx.x * VRC_T + threadIdx.x;
+    if (i >= total) return;                           // total = B * N * W
+    const long long rn = i / W;
+    const int c = (int)(i - rn * W);
+    float acc = 0.f;
+    for (int j = 0; j < k; ++j) {
+        const long long at = (rn * k + j) * W + c;
+        URED_DBG_CHECK(at < total * k);
+        const float m = out[at] > 0.f ? g[at] : 0.f;
+        if (dG) dG[at] = m;
+        acc += m;
+    }
+    dP[rn * 2 * W + c] = acc;
+}
+
+// dP[m][W + c] = sum over the entries idx[n][j] = m, ascending (n, j), of M[(n k + j)][c]: the ordered scatter
+__global__ __launch_bounds__(64) void ef_edge_bwd_scatter_kernel(const float* __restrict__ g, const float* __restrict__ out,
+                                                                 const int* __restrict__ idx, int N, int k, int W, int tiles_n,
+                                                                 float* __restrict__ dP) {
+    __shared__ float acc[SC_P * SC_C];
+    const int ln = threadIdx.x, b = blockIdx.y;
+    const int tn = blockIdx.x % tiles_n, tc = blockIdx.x / tiles_n;
+    const int j0 = tn * SC_P, c = tc * SC_C + ln;
+    const bool cin = c < W;
+    const size_t eb = (size_t)b * N * k;              // N * k < 2^31 (host check)
+#pragma unroll
+    for (int p = 0; p < SC_P; ++p) acc[p * SC_C + ln] = 0.f;
+    scan_add(idx + eb, N * k, j0, ln, acc, [&](int e) -> float {
+        if (!cin) return 0.f;
+        const size_t at = (eb + e) * W + c;
+        URED_DBG_CHECK(at < (size_t)gridDim.y * N * k * W);
+        return out[at] > 0.f ? g[at] : 0.f;
+    });
+    if (!cin) return;
+    for (int p = 0; p < SC_P; ++p) {
+        const int m = j0 + p;
+        if (m >= N) break;
+        const size_t at = ((size_t)b * N + m) * 2 * W + W + c;
+        URED_DBG_CHECK(at < (size_t)gridDim.y * N * 2 * W);
+        dP[at] = acc[p * SC_C + ln];
+    }
+}
+
+// H [B*N*k*r][O] read as [n][j][s][c]: out[(n r + s)][c] = max_j H[((n k + j) r + s)][c], the lowest j on a tie
+__global__ __launch_bounds__(VRC_T) void ef_max_fwd_kernel(const float* __restrict__ H, int k, int r, int O, long long total,
+                                                           float* __restrict__ out, unsigned char* __restrict__ slot) {
+    const long long i = (long long)blockIdx.x * VRC_T + threadIdx.x;
+    if (i >= total) return;                           // total = B * N * r * O
+    const long long q = i / O;                        // n r + s
+    const int c = (int)(i - q * O);
+    const long long n = q / r;
+    const int s = (int)(q - n * r);
+    float best = 0.f;
+    int sl = 0;
+    for (int j = 0; j < k; ++j) {
+        const long long at = ((n * k + j) * r + s) * O + c;
+        URED_DBG_CHECK(at < total * k);
+        const float v = H[at];
+        if (j == 0 || v > best) {
+            best = v;
+            sl = j;
+        }
+    }
+    out[i] = best;
+    slot[i] = (unsigned char)sl;
+}
+
+__global__ __launch_bounds__(VRC_T) void ef_max_bwd_kernel(const float* __restrict__ g, const unsigned char* __restrict__ slot,
+                                                           int k, int r, int O, long long total, float* __restrict__ dH) {
+    const long long i = (long long)blockIdx.x * VRC_T + threadIdx.x;
+    if (i >= total) return;                           // total = B * N * k * r * O
+    const long long t = i / O;                        // (n k + j) r + s
+    const int c = (int)(i - t * O);
+    const long long e = t / r;
+    const int s = (int)(t - e * r);
+    const long long n = e / k;
+    const int j = (int)(e - n * k);
+    const long long from = (n * r + s) * O + c;
+    URED_DBG_CHECK(from * k < total);
+    dH[i] = (int)slot[from] == j ? g[from] : 0.f;
+}
+
+// ---------------- folding ----------------
+
+// out[(n r + s)][c] = max(U[n][c] + T[s][c], 0)
+__global__ __launch_bounds__(VRC_T) void fold_fwd_kernel(const float* __restrict__ U, const float* __restrict__ T, int r, int Co,
+                                                         long long total, float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * VRC_T + threadIdx.x;
+    if (i >= total) return;                           // total = B * N * r * Co
+    const long long q = i / Co;
+    const int c = (int)(i - q * Co);
+    const long long n = q / r;
+    const int s = (int)(q - n * r);
+    out[i] = fmaxf(U[n * Co + c] + T[(long long)s * Co + c], 0.f);
+}
+
+// dU[n][c] = sum_s M[(n r + s)][c], s ascending, M = g where out > 0 else 0
+__global__ __launch_bounds__(VRC_T) void fold_bwd_u_kernel(const float* __restrict__ g, const float* __restrict__ out, int r,
+                                                           int Co, long long total, float* __restrict__ dU) {
+    const long long i = (long long)blockIdx.x * VRC_T + threadIdx.x;
+    if (i >= total) return;                           // total = B * N * Co
+    const long long n = i / Co;
+    const int c = (int)(i - n * Co);
+    float acc = 0.f;
+    for (int s = 0; s < r; ++s) {
+        const long long at = (n * r + s) * Co + c;
+        URED_DBG_CHECK(at < total * r);
+        acc += out[at] > 0.f ? g[at] : 0.f;
+    }
+    dU[i] = acc;
+}
+
+// ws[q][s][c] = sum over the points n of chunk q (ascending) of M[(n r + s)][c]; thread = one (s, c)
+__global__ __launch_bounds__(VRC_T) void fold_bwd_t_kernel(const float* __restrict__ g, const float* __restrict__ out,
+                                                           long long rows, int rc, int chunk, float* __restrict__ ws) {
+    const int col = blockIdx.y * VRC_T + threadIdx.x;
+    if (col >= rc) return;                            // rc = r * Co
+    const long long p0 = (long long)blockIdx.x * chunk;
+    const long long p1 = p0 + chunk < rows ? p0 + chunk : rows;
+    float acc = 0.f;
+    for (long long p = p0; p < p1; ++p) {
+        const long long at = p * rc + col;
+        acc += out[at] > 0.f ? g[at] : 0.f;
+    }
+    URED_DBG_CHECK((long long)blockIdx.x * rc + col < (long long)gridDim.x * rc);
+    ws[(long long)blockIdx.x * rc + col] = acc;
+}
+
 inline unsigned blocks_for(long long n) { return (unsigned)((n + VRC_T - 1) / VRC_T); }
 constexpr long long LIM = 1ll << 31;
+
+int ef_edge_check(const char* who, int B, int N, int k, int W) {
+    URED_REQUIRE(B >= 0 && N >= 1, "%s: bad sizes B=%d N=%d", who, B, N);
+    URED_REQUIRE(k >= 1 && k <= VRC_KMAX, "%s: k %d outside [1, %d]", who, k, VRC_KMAX);
+    URED_REQUIRE(k <= N, "%s: k %d exceeds the cloud's %d points", who, k, N);
+    URED_REQUIRE(W >= 1 && W <= URED_VRC_OMAX * URED_VRC_RMAX, "%s: width %d outside [1, %d]", who, W,
+                 URED_VRC_OMAX * URED_VRC_RMAX);
+    URED_REQUIRE(B <= 65535, "%s: B %d exceeds 65535", who, B);
+    URED_REQUIRE((long long)B * N * k * W < LIM && (long long)B * N * 2 * W < LIM,
+                 "%s: B * N * k * W and 2 * B * N * W must stay below 2^31", who);
+    return 0;
+}
+
+int ef_max_check(const char* who, int B, int N, int k, int r, int O) {
+    URED_REQUIRE(B >= 0 && N >= 1, "%s: bad sizes B=%d N=%d", who, B, N);
+    URED_REQUIRE(k >= 1 && k <= VRC_KMAX, "%s: k %d outside [1, %d]", who, k, VRC_KMAX);
+    URED_REQUIRE(r >= 1 && r <= URED_VRC_RMAX, "%s: step ratio %d outside [1, %d]", who, r, URED_VRC_RMAX);
+    URED_REQUIRE(O >= 1 && O <= URED_VRC_OMAX, "%s: O %d outside [1, %d]", who, O, URED_VRC_OMAX);
+    URED_REQUIRE((long long)B * N * k * r * O < LIM, "%s: B * N * k * r * O = %lld exceeds 2^31 - 1", who,
+                 (long long)B * N * k * r * O);
+    return 0;
+}
+
+int fold_check(const char* who, int B, int N, int r, int Co) {
+    URED_REQUIRE(B >= 0 && N >= 1 && Co >= 1, "%s: bad sizes B=%d N=%d Co=%d", who, B, N, Co);
+    URED_REQUIRE(r >= 1 && r <= URED_VRC_RMAX, "%s: step ratio %d outside [1, %d]", who, r, URED_VRC_RMAX);
+    URED_REQUIRE((long long)B * N * r * Co < LIM, "%s: B * N * r * Co = %lld exceeds 2^31 - 1", who, (long long)B * N * r * Co);
+    return 0;
+}
 
 int sa_check(const char* who, int B, int N, int k, int rel, int mid, int ms) {
     URED_REQUIRE(B >= 0 && N >= 1, "%s: bad sizes B=%d N=%d", who, B, N);
@@ -782,6 +970,83 @@ int ured_vrc_unpool_bwd(const float* g, const int* idx, const float* w, int B, i
         hipLaunchKernelGGL(unpool_bwd_skip_kernel, dim3(blocks_for(total)), dim3(VRC_T), 0, st, g, D2, D1, total, dskip);
     }
     return ured::launch_status("ured_vrc_unpool_bwd");
+}
+
+int ured_vrc_ef_edge_fwd(const float* G, const float* P, const int* idx, int B, int N, int k, int W, float* out, void* stream) {
+    ured::clear_error();
+    if (const int rc = ef_edge_check("ured_vrc_ef_edge_fwd", B, N, k, W)) return rc;
+    if (B == 0) return 0;
+    URED_REQUIRE(P && idx && out, "ured_vrc_ef_edge_fwd: null pointer");
+    const long long total = (long long)B * N * k * W;
+    hipLaunchKernelGGL(ef_edge_fwd_kernel, dim3(blocks_for(total)), dim3(VRC_T), 0, (hipStream_t)stream, G, P, idx, N, k, W,
+                       total, out);
+    return ured::launch_status("ured_vrc_ef_edge_fwd");
+}
+
+int ured_vrc_ef_edge_bwd(const float* g, const float* out, const int* idx, int B, int N, int k, int W, float* dG, float* dP,
+                         void* stream) {
+    ured::clear_error();
+    if (const int rc = ef_edge_check("ured_vrc_ef_edge_bwd", B, N, k, W)) return rc;
+    if (B == 0) return 0;
+    URED_REQUIRE(g && out && idx && dP, "ured_vrc_ef_edge_bwd: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const long long total = (long long)B * N * W;
+    hipLaunchKernelGGL(ef_edge_bwd_point_kernel, dim3(blocks_for(total)), dim3(VRC_T), 0, st, g, out, k, W, total, dG, dP);
+    const int tiles_n = (N + SC_P - 1) / SC_P, tiles_c = (W + SC_C - 1) / SC_C;
+    hipLaunchKernelGGL(ef_edge_bwd_scatter_kernel, dim3((unsigned)tiles_n * (unsigned)tiles_c, B), dim3(64), 0, st, g, out, idx,
+                       N, k, W, tiles_n, dP);
+    return ured::launch_status("ured_vrc_ef_edge_bwd");
+}
+
+int ured_vrc_ef_max_fwd(const float* H, int B, int N, int k, int r, int O, float* out, unsigned char* slot, void* stream) {
+    ured::clear_error();
+    if (const int rc = ef_max_check("ured_vrc_ef_max_fwd", B, N, k, r, O)) return rc;
+    if (B == 0) return 0;
+    URED_REQUIRE(H && out && slot, "ured_vrc_ef_max_fwd: null pointer");
+    const long long total = (long long)B * N * r * O;
+    hipLaunchKernelGGL(ef_max_fwd_kernel, dim3(blocks_for(total)), dim3(VRC_T), 0, (hipStream_t)stream, H, k, r, O, total, out,
+                       slot);
+    return ured::launch_status("ured_vrc_ef_max_fwd");
+}
+
+int ured_vrc_ef_max_bwd(const float* g, const unsigned char* slot, int B, int N, int k, int r, int O, float* dH, void* stream) {
+    ured::clear_error();
+    if (const int rc = ef_max_check("ured_vrc_ef_max_bwd", B, N, k, r, O)) return rc;
+    if (B == 0) return 0;
+    URED_REQUIRE(g && slot && dH, "ured_vrc_ef_max_bwd: null pointer");
+    const long long total = (long long)B * N * k * r * O;
+    hipLaunchKernelGGL(ef_max_bwd_kernel, dim3(blocks_for(total)), dim3(VRC_T), 0, (hipStream_t)stream, g, slot, k, r, O, total,
+                       dH);
+    return ured::launch_status("ured_vrc_ef_max_bwd");
+}
+
+int ured_vrc_fold_fwd(const float* U, const float* T, int B, int N, int r, int Co, float* out, void* stream) {
+    ured::clear_error();
+    if (const int rc = fold_check("ured_vrc_fold_fwd", B, N, r, Co)) return rc;
+    if (B == 0) return 0;
+    URED_REQUIRE(U && T && out, "ured_vrc_fold_fwd: null pointer");
+    const long long total = (long long)B * N * r * Co;
+    hipLaunchKernelGGL(fold_fwd_kernel, dim3(blocks_for(total)), dim3(VRC_T), 0, (hipStream_t)stream, U, T, r, Co, total, out);
+    return ured::launch_status("ured_vrc_fold_fwd");
+}
+
+int ured_vrc_fold_bwd(const float* g, const float* out, int B, int N, int r, int Co, int chunk, float* dU, float* ws,
+                      void* stream) {
+    ured::clear_error();
+    if (const int rc = fold_check("ured_vrc_fold_bwd", B, N, r, Co)) return rc;
+    URED_REQUIRE(chunk >= 1, "ured_vrc_fold_bwd: chunk %d must be at least 1", chunk);
+    if (B == 0) return 0;
+    const long long rows = (long long)B * N, rc = (long long)r * Co;
+    const long long nchunks = (rows + chunk - 1) / chunk;
+    URED_REQUIRE(nchunks * rc < LIM, "ured_vrc_fold_bwd: the dT workspace exceeds 2^31 - 1 elements");
+    URED_REQUIRE((rc + VRC_T - 1) / VRC_T <= 65535, "ured_vrc_fold_bwd: r * Co = %lld exceeds %d", rc, 65535 * VRC_T);
+    URED_REQUIRE(g && out && dU && ws, "ured_vrc_fold_bwd: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const long long total = rows * Co;
+    hipLaunchKernelGGL(fold_bwd_u_kernel, dim3(blocks_for(total)), dim3(VRC_T), 0, st, g, out, r, Co, total, dU);
+    hipLaunchKernelGGL(fold_bwd_t_kernel, dim3((unsigned)nchunks, (unsigned)((rc + VRC_T - 1) / VRC_T)), dim3(VRC_T), 0, st, g,
+                       out, rows, (int)rc, chunk, ws);
+    return ured::launch_status("ured_vrc_fold_bwd");
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
-"""VRCNet's self-attention encoder (Density_aware_Chamfer_Distance/models/vrcnet.py:15-290) on the HIP
-Functions of ured_hip.vrc: SA_module, SK_SA_module, SKN_Res_unit, SA_SKN_Res_encoder and Linear_ResBlock.
+"""VRCNet's self-attention encoder and decoder (Density_aware_Chamfer_Distance/models/vrcnet.py:15-403) on
+the HIP Functions of ured_hip.vrc: SA_module, SK_SA_module, SKN_Res_unit, SA_SKN_Res_encoder,
+Linear_ResBlock, Folding and MSAP_SKN_decoder.
 
 Same names, constructor arguments, parameter names and shapes as the reference (the nn.Conv2d /
 nn.Linear modules only hold the parameters, Conv2d weights stay [out, in, 1, 1]), so a reference
@@ -13,18 +14,29 @@ What differs in how it is computed, not in what:
   - conv1 and conv_res of an SKN_Res_unit read the same input: one GEMM on stacked weights.
   - the global half of conv6 is a per-cloud row bias of the GEMM; the repeat is never built.
   - each level's kNN and FPS run once and are shared by all branches.
-nn.Dropout stays torch's own. EF_expansion, Folding, MSAP_SKN_decoder and Model are not built.
+nn.Dropout stays torch's own.
+
+The decoder (vrcnet.py:54-86, 293-403): Folding and MSAP_SKN_decoder here, EF_expansion in
+chamfer3D/model_utils.py. Folding never builds its [B, G + C + 2, N r] input (row bias + per-point GEMM +
+grid table, FoldFn); the decoder's fully connected and 1x1 layers are linear_rows, FPS on the predicted
+points is ured_hip.group.fps from index 0, the gathers are GroupFn (ordered backward), the score ranking is
+a stable descending sort (lowest index first on a tie; the reference's topk leaves ties open) and
+F.softplus stays torch's own. Only Model (the VAE heads, rsample, the KLD / MMD terms, the loss mix)
+remains unbuilt.
 
 Setting `net.decisions = {}` on a module makes its next forward export the discrete decisions: the
 kNN / FPS / pooling-neighbour / three-NN indices of the encoder, the pre-activation of every ReLU
 ('pre': name -> tensor, the mask is pre > 0) and the pool slots.
 """
+import math
+
 import torch
 import torch.nn as nn
 
-from chamfer3D.model_utils import edge_preserve_sampling_rows, knn, three_nn_upsampling
-from ured_hip.vrc import (CMAX, MaxRowsFn, MMAX, ReluFn, SaFn, SkMeanFn, SkMixFn, UnpoolFn, linear_rows,
-                          sa_check)
+from chamfer3D.model_utils import EF_expansion, edge_preserve_sampling_rows, gen_grid_up, knn, three_nn_upsampling
+from ured_hip.group import GroupFn, fps
+from ured_hip.vrc import (CMAX, CenterFn, FoldFn, MaxRowsFn, MMAX, ReluFn, RMAX, SaFn, SkMeanFn, SkMixFn, UnpoolFn,
+                          linear_rows, sa_check)
 
 
 def _w2(conv):
@@ -282,3 +294,183 @@ class SA_SKN_Res_encoder(nn.Module):
     def forward(self, features):
         B, _, N = features.shape
         return _unrows(self.forward_rows(features), B, N, four=False)
+
+
+class Folding(nn.Module):
+    """Every coarse point becomes step_ratio points: relu(conv([global | point | grid])). The
+    [B, G + C + 2, N r] feature tensor is never built: the global columns of conv are a per-cloud row bias,
+    the point columns one GEMM per coarse point (U), the grid columns a [r, output_size] table (T), and
+    FoldFn computes relu(U[n] + T[s])."""
+
+    def __init__(self, input_size, output_size, step_ratio, global_feature_size=1024, num_models=1):
+        super().__init__()
+        if num_models != 1:
+            raise ValueError(f"Folding: num_models {num_models} is not supported (the reference's configurations use 1)")
+        if not 1 <= step_ratio <= RMAX:
+            raise ValueError(f"Folding: step_ratio {step_ratio} outside [1, {RMAX}]")
+        self.input_size = input_size
+        self.output_size = output_size
+        self.step_ratio = step_ratio
+        self.num_models = num_models
+        self.global_feature_size = global_feature_size
+        self.conv = nn.Conv1d(input_size + global_feature_size + 2, output_size, 1, bias=True)
+        # [r, 2], x slowest: the reference's meshgrid over num_x x num_y points of +-0.2
+        self.register_buffer("grid", gen_grid_up(step_ratio, 0.2).t().contiguous(), persistent=False)
+
+    def forward_rows(self, point_rows, global_feat, rec=None, tag="fold"):
+        """point_rows [B*N, C], global_feat [B, G] -> [B*N*r, output_size], row n r + s."""
+        C, G = self.input_size, self.global_feature_size
+        if global_feat.dim() != 2 or global_feat.shape[1] != G:
+            raise ValueError(f"Folding: global_feat must be [B, {G}], got {tuple(global_feat.shape)}")
+        B = global_feat.shape[0]
+        if point_rows.dim() != 2 or point_rows.shape[1] != C or point_rows.shape[0] % B or point_rows.shape[0] < B:
+            raise ValueError(f"Folding: point rows must be [B*N, {C}] for B = {B}, got {tuple(point_rows.shape)}")
+        N = point_rows.shape[0] // B
+        W = self.conv.weight.view(self.output_size, G + C + 2)
+        Rb = linear_rows(global_feat, W[:, :G])
+        U = linear_rows(point_rows, W[:, G:G + C], self.conv.bias, rowbias=Rb, group_rows=N)
+        T = linear_rows(self.grid, W[:, G + C:])
+        out = FoldFn.apply(U, T)
+        _note(rec, tag, out)
+        return out
+
+    def forward(self, point_feat, global_feat):
+        B, C, N = point_feat.shape
+        rec = getattr(self, "decisions", None)
+        y = self.forward_rows(point_feat.transpose(1, 2).reshape(B * N, C), global_feat, rec if isinstance(rec, dict) else None)
+        return y.view(B, N * self.step_ratio, self.output_size).transpose(1, 2)
+
+
+def rank_scores(scores, num):
+    """scores [B, M] -> int32 [B, num]: the num highest, descending, the lowest index first on a tie."""
+    return torch.sort(scores, dim=1, descending=True, stable=True)[1][:, :num].int()
+
+
+def _take(rows, B, idx):
+    """rows [B*N, C], idx int32 [B, S] -> [B*S, C], with GroupFn's ordered backward."""
+    return GroupFn.apply(None, None, rows.view(B, rows.shape[0] // B, -1), idx.unsqueeze(2).contiguous())
+
+
+class MSAP_SKN_decoder(nn.Module):
+    """The coarse-to-fine decoder: a global code and a partial cloud -> (coarse_raw [B, 3, num_coarse_raw],
+    coarse_high [B, 3, (num_coarse_raw + n) up_scale], coarse [B, 3, num_coarse], fine [B, 3, num_fine]).
+    pts_num (not in the reference) is handed to the encoder; None keeps the reference's sizes.
+    The score selection ranks softplus(score) descending with the lowest index first on a tie.
+    `decisions = {}` exports: 'enc' (the encoder's own record), 'knn' / 'slot' / 'H' per EF unit, 'fps',
+    'topk', 'scores', and 'pre' (name -> the tensor whose sign is a ReLU mask)."""
+
+    def __init__(self, num_coarse_raw, num_fps, num_coarse, num_fine, layers=[2, 2, 2, 2], knn_list=[10, 20], pk=10,
+                 points_label=False, local_folding=False, over_scale=1, pts_num=None):
+        super().__init__()
+        self.num_coarse_raw = num_coarse_raw
+        self.num_fps = num_fps
+        self.num_coarse = num_coarse
+        self.num_fine = num_fine
+        self.points_label = points_label
+        self.local_folding = local_folding
+        self.fc1 = nn.Linear(1024, 1024)
+        self.fc2 = nn.Linear(1024, 1024)
+        self.fc3 = nn.Linear(1024, num_coarse_raw * 3)
+        self.dense_feature_size = 256
+        self.expand_feature_size = 64
+        self.input_size = 4 if points_label else 3
+        self.encoder = SA_SKN_Res_encoder(input_size=self.input_size, k=knn_list, pk=pk, output_size=self.dense_feature_size,
+                                          layers=layers, **({} if pts_num is None else {"pts_num": list(pts_num)}))
+        self.up_scale = int(math.ceil(num_fine / (num_coarse_raw + 2048))) * over_scale
+        if self.up_scale >= 2:
+            self.expansion1 = EF_expansion(input_size=self.dense_feature_size, output_size=self.expand_feature_size,
+                                           step_ratio=self.up_scale, k=4)
+            self.conv_cup1 = nn.Conv1d(self.expand_feature_size, self.expand_feature_size, 1)
+        else:
+            self.expansion1 = None
+            self.conv_cup1 = nn.Conv1d(self.dense_feature_size, self.expand_feature_size, 1)
+        self.conv_cup2 = nn.Conv1d(self.expand_feature_size, 3, 1, bias=True)
+        self.conv_s1 = nn.Conv1d(self.expand_feature_size, 16, 1, bias=True)
+        self.conv_s2 = nn.Conv1d(16, 8, 1, bias=True)
+        self.conv_s3 = nn.Conv1d(8, 1, 1, bias=True)
+        if self.local_folding:
+            self.expansion2 = Folding(input_size=self.expand_feature_size, output_size=self.dense_feature_size,
+                                      step_ratio=(num_fine // num_coarse))
+        else:
+            self.expansion2 = EF_expansion(input_size=self.expand_feature_size, output_size=self.dense_feature_size,
+                                           step_ratio=(num_fine // num_coarse), k=4)
+        self.conv_f1 = nn.Conv1d(self.dense_feature_size, self.expand_feature_size, 1)
+        self.conv_f2 = nn.Conv1d(self.expand_feature_size, 3, 1)
+        self.af = nn.ReLU(inplace=False)
+
+    def forward(self, global_feat, point_input):
+        if global_feat.dim() != 2 or global_feat.shape[1] != 1024:
+            raise ValueError(f"MSAP_SKN_decoder: global_feat must be [B, 1024], got {tuple(global_feat.shape)}")
+        B = global_feat.shape[0]
+        if point_input.dim() != 3 or point_input.shape[0] != B or point_input.shape[1] != 3:
+            raise ValueError(f"MSAP_SKN_decoder: point_input must be [{B}, 3, n], got {tuple(point_input.shape)}")
+        rec = getattr(self, "decisions", None)
+        rec = rec if isinstance(rec, dict) else None
+        ncr = self.num_coarse_raw
+        a1 = linear_rows(global_feat, self.fc1.weight, self.fc1.bias)
+        a2 = linear_rows(a1, self.fc2.weight, self.fc2.bias, relu_in=True)
+        coarse_raw = linear_rows(a2, self.fc3.weight, self.fc3.bias, relu_in=True).view(B, 3, ncr)
+        _note(rec, "fc1", a1)
+        _note(rec, "fc2", a2)
+        org = point_input
+        if self.points_label:
+            coarse_input = torch.cat((coarse_raw, coarse_raw.new_zeros(B, 1, ncr)), 1)
+            org = torch.cat((org, org.new_ones(B, 1, org.shape[2])), 1)
+        else:
+            coarse_input = coarse_raw
+        points = torch.cat((coarse_input, org), 2)
+        if rec is not None:
+            self.encoder.decisions = {}
+        x = self.encoder.forward_rows(points)                                 # [B*N, 256]
+        if rec is not None:
+            rec["enc"] = self.encoder.decisions
+            del self.encoder.decisions
+        N = points.shape[2]
+        if self.up_scale >= 2:
+            x = self.expansion1.forward_rows(x, B, rec, "exp1")
+            N *= self.up_scale
+        c1 = linear_rows(x, _w2(self.conv_cup1), self.conv_cup1.bias)
+        _note(rec, "cup1", c1)
+        feat = ReluFn.apply(c1)                                               # coarse_features [B*N, 64]
+        high = linear_rows(feat, _w2(self.conv_cup2), self.conv_cup2.bias)    # coarse_high [B*N, 3]
+        pts = high
+        if N > self.num_fps:
+            idx_fps = fps(high.detach().view(B, N, 3), self.num_fps, start=torch.zeros(B, dtype=torch.int32, device=high.device))
+            if rec is not None:
+                rec["fps"] = idx_fps
+            pts, feat = _take(high, B, idx_fps), _take(feat, B, idx_fps)
+            N = self.num_fps
+        if rec is not None:
+            rec["coarse_fps"] = pts
+        if N > self.num_coarse:
+            with torch.no_grad():                                             # the scores feed the selection only
+                s = linear_rows(feat.detach(), _w2(self.conv_s1), self.conv_s1.bias)
+                s = linear_rows(s, _w2(self.conv_s2), self.conv_s2.bias, relu_in=True)
+                s = linear_rows(s, _w2(self.conv_s3), self.conv_s3.bias, relu_in=True)
+                scores = torch.nn.functional.softplus(s).view(B, N)
+                idx_scores = rank_scores(scores, self.num_coarse)
+            if rec is not None:
+                rec["scores"], rec["topk"] = scores, idx_scores
+            pts, feat = _take(pts, B, idx_scores), _take(feat, B, idx_scores)
+            N = self.num_coarse
+        coarse = pts
+        if N < self.num_fine:
+            n_fine = N * self.expansion2.step_ratio
+            if self.local_folding and n_fine != self.num_fine:
+                raise ValueError(f"MSAP_SKN_decoder: {N} coarse points x {self.expansion2.step_ratio} is not num_fine "
+                                 f"{self.num_fine}")
+            if self.local_folding:
+                up = self.expansion2.forward_rows(feat, global_feat, rec, "fold")
+            else:
+                up = self.expansion2.forward_rows(feat, B, rec, "exp2")
+            f1 = linear_rows(up, _w2(self.conv_f1), self.conv_f1.bias)
+            _note(rec, "f1", f1)
+            fine = linear_rows(f1, _w2(self.conv_f2), self.conv_f2.bias, relu_in=True)
+            if self.local_folding:
+                fine = CenterFn.apply(fine, coarse)
+        else:
+            if N != self.num_fine:
+                raise ValueError(f"MSAP_SKN_decoder: {N} coarse points exceed num_fine {self.num_fine}")
+            fine, n_fine = coarse, N
+        return (coarse_raw, _unrows(high, B, high.shape[0] // B, four=False), _unrows(coarse, B, N, four=False),
+                _unrows(fine, B, n_fine, four=False))

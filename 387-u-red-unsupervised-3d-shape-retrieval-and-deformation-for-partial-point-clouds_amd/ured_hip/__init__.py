@@ -17,7 +17,8 @@
   vn       Vector-Neuron DGCNN layers: knn_rows, VnEdgeFn, VnPointFn, VnMaxPoolFn, VnFrameFn, VnLinearFn
   dcd      density-aware chamfer as a training loss: DcdLossFn / dcd_loss (one launch each way after the NN)
   pcn      the PCN completion network: PcnEncoderFn, PcnDecoderFn and the fold / pool / ReLU kernels
-  vrc      VRCNet's self-attention encoder: SaFn, SkMeanFn, SkMixFn, EdgePoolFn, UnpoolFn, LinearRowsFn
+  vrc      VRCNet's self-attention encoder and decoder: SaFn, SkMeanFn, SkMixFn, EdgePoolFn, UnpoolFn,
+           LinearRowsFn, and the expansion units' EfEdgeFn, EfMaxFn, FoldFn, CenterFn
   losshead the step's loss head (chamfer families, contrastive, residual, reconstruction, weighted sum)
 """
 from . import _lib, attn, dcd, gcn, group, interp, kernels, losshead, nn, node, occ, ops, optim, pcn, syncbn, vn, vrc  # noqa: F401

@@ -11,6 +11,10 @@ SkMeanFn    s[b][c] = mean over points of sum_i relu(y_i): the input of SK_SA_mo
 SkMixFn     relu?(sum_i a[b][i][c] relu(y_i)): the selected feature.
 EdgePoolFn  centre row | max over the pk neighbour rows (lowest j on a tie), with the winning slot.
 UnpoolFn    three-point interpolation with given weights | skip features.
+EfEdgeFn    the per-edge rows of EF_expansion, relu((G +) centre[n] + neighbour[idx[n, j]]) from the per-point
+            halves of conv1 / conv2; no [B, 2C, k, N] or [B, O + 2C, k, N] tensor exists.
+EfMaxFn     the max over the k slots of conv3's rows (lowest j on a tie), with the winning slot.
+FoldFn      relu(U[n] + T[s]) over the r grid points of every coarse point (Folding).
 LinearRowsFn / ReluFn / MaxRowsFn  the GEMM layers between them (bias, ReLU prologue, per-cloud row
             bias), the ReLU and the max over a cloud's points.
 Arguments are validated before any device work; a tensor off the device raises (no CPU path).
@@ -23,7 +27,7 @@ from torch.autograd import Function
 
 from . import _lib
 from . import kernels as K
-from .pcn import _Relu, pool_bwd, relu
+from .pcn import _Relu, center_bwd, center_fwd, pool_bwd, relu
 
 _P, _I = ctypes.c_void_p, ctypes.c_int
 _lib.register({
@@ -37,13 +41,21 @@ _lib.register({
     "ured_vrc_pool_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
     "ured_vrc_unpool_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
     "ured_vrc_unpool_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
+    "ured_vrc_ef_edge_fwd": [_P, _P, _P, _I, _I, _I, _I, _P, _P],
+    "ured_vrc_ef_edge_bwd": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
+    "ured_vrc_ef_max_fwd": [_P, _I, _I, _I, _I, _I, _P, _P, _P],
+    "ured_vrc_ef_max_bwd": [_P, _P, _I, _I, _I, _I, _I, _P, _P],
+    "ured_vrc_fold_fwd": [_P, _P, _I, _I, _I, _I, _P, _P],
+    "ured_vrc_fold_bwd": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
 })
 
 KMAX, RELMAX, MIDMAX, MSMAX, MMAX, PKMAX = 32, 32, 128, 16, 4, 32      # URED_VRC_* (include/ured_hip.h)
-CMAX = 512                          # the widest SA_module input (the encoder's deepest level)
+CMAX = 512                          # URED_VRC_CMAX: the widest SA_module / EF_expansion input
+OMAX, RMAX = 256, 16                # URED_VRC_OMAX, URED_VRC_RMAX: EF_expansion's output_size and step_ratio
 MAX_B = 65535
 _LIM = 1 << 31
 WA_MIN_CHUNK, WA_CHUNKS = 32, 1024  # points per workgroup of the dWa partials: at least 32, about 1024 workgroups
+FOLD_MIN_CHUNK, FOLD_CHUNKS = 32, 256   # the same for the dT partials of FoldFn
 
 
 def _p(t):
@@ -303,6 +315,158 @@ class UnpoolFn(Function):
         ds = torch.empty(B, N, D1, device=g.device) if D1 else None
         _lib.call("ured_vrc_unpool_bwd", _p(g), _p(idx), _p(weight), B, N, S, Kq, D2, D1, _p(d2), _p(ds), _lib.stream_of(g))
         return d2, None, None, ds
+
+
+def ef_check(who, B, N, k, W):
+    """The limits of the edge-row kernels; W is the row width (O, or O * step_ratio)."""
+    if not 1 <= k <= KMAX:
+        raise ValueError(f"{who}: k {k} outside [1, {KMAX}]")
+    if k > N:
+        raise ValueError(f"{who}: k {k} exceeds the cloud's {N} points")
+    if not 1 <= W <= OMAX * RMAX:
+        raise ValueError(f"{who}: width {W} outside [1, {OMAX * RMAX}]")
+    if B < 1 or B > MAX_B:
+        raise ValueError(f"{who}: B {B} outside [1, {MAX_B}]")
+    if B * N * k * W >= _LIM or 2 * B * N * W >= _LIM:
+        raise ValueError(f"{who}: B * N * k * W and 2 * B * N * W must stay below 2^31")
+
+
+class EfEdgeFn(Function):
+    """(P [B*N, 2 W] = [centre | neighbour], idx int32 [B, N, k], G [B*N*k, W] | None) -> [B*N*k, W]:
+    relu((G[(n, j)] + P[n, :W]) + P[idx[n, j], W:]); an index outside [0, N) reads as a zero neighbour row
+    and takes no gradient. The backward returns dP (centre half summed over j, neighbour half scattered in
+    ascending (n, j)) and dG. record: optional dict that receives the output."""
+
+    @staticmethod
+    def forward(ctx, P, idx, G=None, record=None):
+        who = "EfEdgeFn"
+        _i32(who, "idx", idx, (None, None, None))
+        B, N, k = idx.shape
+        _f32(who, "P", P, (B * N, None))
+        if P.shape[1] < 2 or P.shape[1] % 2:
+            raise ValueError(f"{who}: P has {P.shape[1]} columns, expected [centre | neighbour] halves")
+        W = P.shape[1] // 2
+        ef_check(who, B, N, k, W)
+        if G is not None:
+            _f32(who, "G", G, (B * N * k, W))
+        _lib.require_device(P, idx, G)
+        P, idx = P.contiguous(), idx.contiguous()
+        G = None if G is None else G.contiguous()
+        out = torch.empty(B * N * k, W, device=P.device)
+        _lib.call("ured_vrc_ef_edge_fwd", _p(G), _p(P), _p(idx), B, N, k, W, _p(out), _lib.stream_of(P))
+        if record is not None:
+            record["out"] = out
+        ctx.save_for_backward(idx, out)
+        ctx.dims = (B, N, k, W, G is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        idx, out = ctx.saved_tensors
+        B, N, k, W, has_g = ctx.dims
+        g = g.contiguous()
+        dP = torch.empty(B * N, 2 * W, device=g.device)
+        dG = torch.empty_like(out) if has_g else None
+        _lib.call("ured_vrc_ef_edge_bwd", _p(g), _p(out), _p(idx), B, N, k, W, _p(dG), _p(dP), _lib.stream_of(g))
+        return dP, None, dG, None
+
+
+class EfMaxFn(Function):
+    """(H [B*N*k*r, O] read as [n, j, s, c], B, N, k, r) -> (out [B*N*r, O] = max over j, slot uint8 [B*N*r, O],
+    the lowest j on a tie); the winner alone takes the gradient."""
+
+    @staticmethod
+    def forward(ctx, H, B, N, k, r):
+        who = "EfMaxFn"
+        B, N, k, r = int(B), int(N), int(k), int(r)
+        if B < 1 or N < 1:
+            raise ValueError(f"{who}: bad sizes B={B} N={N}")
+        if not 1 <= k <= KMAX:
+            raise ValueError(f"{who}: k {k} outside [1, {KMAX}]")
+        if not 1 <= r <= RMAX:
+            raise ValueError(f"{who}: step ratio {r} outside [1, {RMAX}]")
+        _f32(who, "H", H, (B * N * k * r, None))
+        O = H.shape[1]
+        if not 1 <= O <= OMAX:
+            raise ValueError(f"{who}: O {O} outside [1, {OMAX}]")
+        if B * N * k * r * O >= _LIM:
+            raise ValueError(f"{who}: B * N * k * r * O must stay below 2^31")
+        _lib.require_device(H)
+        H = H.contiguous()
+        out = torch.empty(B * N * r, O, device=H.device)
+        slot = torch.empty(B * N * r, O, dtype=torch.uint8, device=H.device)
+        _lib.call("ured_vrc_ef_max_fwd", _p(H), B, N, k, r, O, _p(out), _p(slot), _lib.stream_of(H))
+        ctx.save_for_backward(slot)
+        ctx.dims = (B, N, k, r, O)
+        ctx.mark_non_differentiable(slot)
+        return out, slot
+
+    @staticmethod
+    def backward(ctx, g, _gs):
+        slot, = ctx.saved_tensors
+        B, N, k, r, O = ctx.dims
+        g = g.contiguous()
+        dH = torch.empty(B * N * k * r, O, device=g.device)
+        _lib.call("ured_vrc_ef_max_bwd", _p(g), _p(slot), B, N, k, r, O, _p(dH), _lib.stream_of(g))
+        return dH, None, None, None, None
+
+
+class FoldFn(Function):
+    """(U [R, Co], T [r, Co]) -> relu(U[n] + T[s]) [R * r, Co], row n r + s. dU sums over s ascending; dT from
+    per-chunk partials (points ascending inside a chunk), then the column sums over the chunks."""
+
+    @staticmethod
+    def forward(ctx, U, T):
+        who = "FoldFn"
+        _f32(who, "U", U, (None, None))
+        R, Co = U.shape
+        _f32(who, "T", T, (None, Co))
+        r = T.shape[0]
+        if not 1 <= r <= RMAX:
+            raise ValueError(f"{who}: step ratio {r} outside [1, {RMAX}]")
+        if R < 1 or Co < 1 or R * r * Co >= _LIM:
+            raise ValueError(f"{who}: bad sizes R={R} Co={Co} (R * r * Co must stay below 2^31)")
+        _lib.require_device(U, T)
+        U, T = U.contiguous(), T.contiguous()
+        out = torch.empty(R * r, Co, device=U.device)
+        _lib.call("ured_vrc_fold_fwd", _p(U), _p(T), 1, R, r, Co, _p(out), _lib.stream_of(U))
+        ctx.save_for_backward(out)
+        ctx.dims = (R, r, Co)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        out, = ctx.saved_tensors
+        R, r, Co = ctx.dims
+        g = g.contiguous()
+        chunk = max(FOLD_MIN_CHUNK, (R + FOLD_CHUNKS - 1) // FOLD_CHUNKS)
+        nch = (R + chunk - 1) // chunk
+        dU = torch.empty(R, Co, device=g.device)
+        ws = torch.empty(nch, r * Co, device=g.device)
+        _lib.call("ured_vrc_fold_bwd", _p(g), _p(out), 1, R, r, Co, chunk, _p(dU), _p(ws), _lib.stream_of(g))
+        return dU, K.colsum(ws).view(r, Co)
+
+
+class CenterFn(Function):
+    """(y [R*r, 3], cp [R, 3]) -> y[n r + s] + cp[n] (ured_pcn_center_fwd); dcp sums over s ascending."""
+
+    @staticmethod
+    def forward(ctx, y, cp):
+        who = "CenterFn"
+        _f32(who, "cp", cp, (None, 3))
+        R = cp.shape[0]
+        _f32(who, "y", y, (None, 3))
+        if R < 1 or y.shape[0] < R or y.shape[0] % R or y.shape[0] // R > RMAX:
+            raise ValueError(f"{who}: {y.shape[0]} rows are not 1..{RMAX} copies of {R} centres")
+        _lib.require_device(y, cp)
+        ctx.dims = (R, y.shape[0] // R)
+        return center_fwd(y.contiguous(), cp.contiguous(), 1, R, y.shape[0] // R)
+
+    @staticmethod
+    def backward(ctx, g):
+        R, r = ctx.dims
+        g = g.contiguous()
+        return g, center_bwd(g, None, 1, R, r)
 
 
 class ReluFn(Function):

@@ -51,6 +51,9 @@
  *                       <- the attention core of SA_module, the branch selection of SK_SA_module,
  *                       edge_preserve_sampling's gather + max and three_interpolate
  *                       (Density_aware_Chamfer_Distance/models/vrcnet.py:15-290) and their autograd.
+ *   ured_vrc_ef_edge_fwd / ured_vrc_ef_edge_bwd / ured_vrc_ef_max_fwd / ured_vrc_ef_max_bwd / ured_vrc_fold_fwd /
+ *   ured_vrc_fold_bwd   <- the per-edge part of EF_expansion (utils/model_utils.py:137-166) and Folding's
+ *                       repeat + concatenation + ReLU (models/vrcnet.py:54-86) and their autograd.
  */
 #ifndef URED_HIP_H
 #define URED_HIP_H
@@ -63,7 +66,7 @@ extern "C" {
 #define URED_EINVAL 1001
 
 /* Library identification: returns URED_ABI_VERSION. */
-#define URED_ABI_VERSION 17  /* 17: ured_vrc_sa_fwd / ured_vrc_sa_bwd / ured_vrc_sk_mean_fwd / ured_vrc_sk_mean_bwd / ured_vrc_sk_mix_fwd / ured_vrc_sk_mix_bwd / ured_vrc_pool_fwd / ured_vrc_pool_bwd / ured_vrc_unpool_fwd / ured_vrc_unpool_bwd; 16: ured_dcd_loss_fwd / ured_dcd_loss_bwd, ured_pcn_relu / ured_pcn_pool_bwd / ured_pcn_fold_fwd / ured_pcn_fold_bwd / ured_pcn_center_fwd / ured_pcn_center_bwd; 15:ured_vn_parts / ured_vn_knn / ured_vn_act_fwd / ured_vn_act_bwd / ured_vn_maxpool_fwd / ured_vn_maxpool_bwd / ured_vn_frame_fwd / ured_vn_frame_bwd; 14: ured_gcn_dirs / ured_gcn_conv_fwd / ured_gcn_conv_bwd / ured_gcn_conv_bwd_parts / ured_gcn_pool_fwd / ured_gcn_pool_bwd; 13: ured_interp_fwd / ured_interp_bwd; 12: ured_fps / ured_ball_query / ured_group_fwd / ured_group_bwd; 11: ured_knn_fwd / ured_knn_bwd; 10: ured_occlude; 9: ured_attn_fwd_sets / ured_attn_bwd_sets, ured_get_shape_src_fwd / _bwd; 8: ured_nn_bwd_set; 7: ured_copy_batch; 6: ured_part_rows_bwd_add; 5: node BN SyncBN fields (stats_out/stats_in, sums_out/sums_in); ured_bn_stats et al. */
+#define URED_ABI_VERSION 18  /* 18: ured_vrc_ef_edge_fwd / ured_vrc_ef_edge_bwd / ured_vrc_ef_max_fwd / ured_vrc_ef_max_bwd / ured_vrc_fold_fwd / ured_vrc_fold_bwd; 17: ured_vrc_sa_fwd / ured_vrc_sa_bwd / ured_vrc_sk_mean_fwd / ured_vrc_sk_mean_bwd / ured_vrc_sk_mix_fwd / ured_vrc_sk_mix_bwd / ured_vrc_pool_fwd / ured_vrc_pool_bwd / ured_vrc_unpool_fwd / ured_vrc_unpool_bwd; 16: ured_dcd_loss_fwd / ured_dcd_loss_bwd, ured_pcn_relu / ured_pcn_pool_bwd / ured_pcn_fold_fwd / ured_pcn_fold_bwd / ured_pcn_center_fwd / ured_pcn_center_bwd; 15:ured_vn_parts / ured_vn_knn / ured_vn_act_fwd / ured_vn_act_bwd / ured_vn_maxpool_fwd / ured_vn_maxpool_bwd / ured_vn_frame_fwd / ured_vn_frame_bwd; 14: ured_gcn_dirs / ured_gcn_conv_fwd / ured_gcn_conv_bwd / ured_gcn_conv_bwd_parts / ured_gcn_pool_fwd / ured_gcn_pool_bwd; 13: ured_interp_fwd / ured_interp_bwd; 12: ured_fps / ured_ball_query / ured_group_fwd / ured_group_bwd; 11: ured_knn_fwd / ured_knn_bwd; 10: ured_occlude; 9: ured_attn_fwd_sets / ured_attn_bwd_sets, ured_get_shape_src_fwd / _bwd; 8: ured_nn_bwd_set; 7: ured_copy_batch; 6: ured_part_rows_bwd_add; 5: node BN SyncBN fields (stats_out/stats_in, sums_out/sums_in); ured_bn_stats et al. */
 int ured_abi_version(void);
 /* Thread-local message for the last failing call on this thread ("" if none). */
 const char* ured_last_error(void);
@@ -869,6 +872,40 @@ int ured_vrc_unpool_fwd(const float* feat2, const int* idx, const float* w, cons
                         int D2, int D1, float* out, void* stream);
 int ured_vrc_unpool_bwd(const float* g, const int* idx, const float* w, int B, int N, int S, int K, int D2, int D1,
                         float* dfeat2, float* dskip, void* stream);
+
+/* The decoder's expansion units (EF_expansion, Density_aware_Chamfer_Distance/utils/model_utils.py:137-166;
+ * Folding, models/vrcnet.py:54-86). The 1x1 convolutions on [centre | neighbour] features commute with the
+ * gather, so their two halves are per-point GEMMs and only these kernels run per edge.
+ *
+ * ured_vrc_ef_edge_fwd: P [B*N][2 W] = [centre half | neighbour half], idx int32 [B][N][k], G [B*N*k][W] or null:
+ *   out[(n k + j)][c] = max((G[(n k + j)][c] + P[n][c]) + P[idx[n][j]][W + c], 0); without G the first add
+ *   drops out. An index outside [0, N) reads as a zero neighbour row.
+ *   Limits: 1 <= k <= min(32, N), W <= URED_VRC_OMAX * URED_VRC_RMAX.
+ * ured_vrc_ef_edge_bwd: with M = g where out > 0 else 0 ([B*N*k][W]):
+ *   dG = M (written when dG is not null); dP[n][c] = sum_j M[(n k + j)][c], j ascending;
+ *   dP[m][W + c] = sum over the entries idx[n][j] = m, ascending (n, j), of M[(n k + j)][c].
+ *   Every element of dP is written; a point no row names gets 0 in the neighbour half; an index outside
+ *   [0, N) takes no gradient.
+ * ured_vrc_ef_max_fwd: H [B*N*k*r][O] read as [n][j][s][c] (the rows of conv3 on the [B*N*k][O r] rows of
+ *   conv2, a view of the same memory): out[(n r + s)][c] = max_j H[((n k + j) r + s)][c],
+ *   slot[(n r + s)][c] = the winning j, the lowest on a tie. k <= 32, r <= URED_VRC_RMAX, O <= URED_VRC_OMAX.
+ * ured_vrc_ef_max_bwd: dH[((n k + j) r + s)][c] = g[(n r + s)][c] where slot[(n r + s)][c] = j else 0.
+ *
+ * ured_vrc_fold_fwd: out[(n r + s)][c] = max(U[n][c] + T[s][c], 0), U [B*N][Co], T [r][Co]; r <= URED_VRC_RMAX.
+ * ured_vrc_fold_bwd: with M = g where out > 0 else 0: dU[n][c] = sum_s M[(n r + s)][c], s ascending;
+ *   ws[q][s][c] = sum over the points n of chunk q (n / chunk = q, ascending) of M[(n r + s)][c]
+ *   ([ceil(B*N / chunk)][r][Co]; the caller sums the chunks). */
+#define URED_VRC_CMAX 512
+#define URED_VRC_OMAX 256
+#define URED_VRC_RMAX 16
+int ured_vrc_ef_edge_fwd(const float* G, const float* P, const int* idx, int B, int N, int k, int W, float* out, void* stream);
+int ured_vrc_ef_edge_bwd(const float* g, const float* out, const int* idx, int B, int N, int k, int W, float* dG, float* dP,
+                         void* stream);
+int ured_vrc_ef_max_fwd(const float* H, int B, int N, int k, int r, int O, float* out, unsigned char* slot, void* stream);
+int ured_vrc_ef_max_bwd(const float* g, const unsigned char* slot, int B, int N, int k, int r, int O, float* dH, void* stream);
+int ured_vrc_fold_fwd(const float* U, const float* T, int B, int N, int r, int Co, float* out, void* stream);
+int ured_vrc_fold_bwd(const float* g, const float* out, int B, int N, int r, int Co, int chunk, float* dU, float* ws,
+                      void* stream);
 
 /* ---------------- loss head (csrc/loss.hip) ---------------- */
 /* compute_cm_loss of the deformed shape `out` [B,S,3] and of its mirror image (x -> -x,

@@ -7,7 +7,10 @@ the first level's rows whose neighbour set differs between the two versions' sea
 Shapes are those of cfgs/vrc_dcd.yaml: N 3072, k 16, pk 10, layers 1,1,1,1, 4 input channels, 32 clouds.
 Legs: one SA unit at the first level (C 64: rel 4, mid 16) forward + backward; one edge pool
 (3072 -> 1536 points, C 64) forward + backward; one unpool (1536 -> 3072 points, 128 interpolated + 64
-skip channels) forward + backward; the whole encoder forward + backward. The baselines, written out
+skip channels) forward + backward; the whole encoder forward + backward; and, at the shape of cfgs/vrc.yaml
+(2048 input points, num_coarse_raw 1024, num_fps 2048, num_coarse 1024, folding, points_label): Folding +
+conv_f1 / conv_f2 (1024 -> 2048 points) forward + backward against the [B, G + C + 2, N r] tensor built in
+full, and the whole decoder forward + backward. The baselines, written out
 below: the gathered [B, C, k, N] tensor with conv2 / conv3 run on it, the attention weights repeated
 over share_planes, all kept by autograd; the gathered [B, C, S, pk] tensor and its max; three gathered
 rows times their weights; for the encoder those pieces with the module's own parameters, the
@@ -32,7 +35,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N, KNN, PK, CIN = 3072, 16, 10, 4
 PTS = [3072, 1536, 768, 384]
 LEGS = ["SA unit fwd+bwd C64 k16", "edge pool fwd+bwd 3072->1536 C64 pk10", "unpool fwd+bwd 1536->3072 128+64",
-        "encoder fwd+bwd"]
+        "encoder fwd+bwd", "Folding + conv_f1/f2 fwd+bwd 1024->2048", "decoder fwd+bwd"]
+# the decoder legs: cfgs/vrc.yaml (2048 input points, num_coarse_raw 1024, num_fps 2048, num_coarse 1024, folding, points_label)
+DEC = dict(n=2048, num_coarse_raw=1024, num_fps=2048, num_coarse=1024, num_fine=2048)
 
 
 # ---------------- the torch baselines (the reference's layouts: [B, C, 1, N]) ----------------
@@ -123,6 +128,59 @@ def encoder_torch(net, feats):
         u = unpool_torch(F.relu(y).squeeze(2), idx, inv / inv.sum(2, keepdim=True), skip.squeeze(2)).unsqueeze(2)
         y = F.conv2d(u, conv.weight, conv.bias)
     return F.conv2d(F.relu(y), net.conv_out.weight, net.conv_out.bias).squeeze(2)
+
+
+def folding_torch(m, point_feat, global_feat):
+    """Folding on the [B, G + C + 2, N r] tensor built in full. point_feat [B, C, N], global_feat [B, G]."""
+    import torch
+    import torch.nn.functional as F
+    Bn, _, Nn = point_feat.shape
+    r = m.step_ratio
+    feats = torch.cat((global_feat.unsqueeze(2).expand(-1, -1, Nn * r), point_feat.repeat_interleave(r, dim=2),
+                       m.grid.t().repeat(1, Nn).unsqueeze(0).expand(Bn, -1, -1)), 1)
+    return F.relu(F.conv1d(feats, m.conv.weight, m.conv.bias))
+
+
+def fold_tail_torch(dec, feat, g):
+    """expansion2 (Folding) + conv_f1 + conv_f2 -> [B, 3, N r]."""
+    import torch.nn.functional as F
+    up = folding_torch(dec.expansion2, feat, g)
+    return F.conv1d(F.relu(F.conv1d(up, dec.conv_f1.weight, dec.conv_f1.bias)), dec.conv_f2.weight, dec.conv_f2.bias)
+
+
+def fold_tail_hip(dec, rows, g):
+    """The same layers as the decoder runs them: rows [B*N, C] -> [B*N*r, 3]."""
+    from ured_hip.vrc import linear_rows
+    up = dec.expansion2.forward_rows(rows, g)
+    f1 = linear_rows(up, dec.conv_f1.weight.squeeze(2), dec.conv_f1.bias)
+    return linear_rows(f1, dec.conv_f2.weight.squeeze(2), dec.conv_f2.bias, relu_in=True)
+
+
+def decoder_torch(net, g, pin):
+    """The folding / points_label decoder without an expansion1, in torch: encoder_torch, topk for the ranking,
+    torch.gather, the project's FPS kernel (torch has none)."""
+    import torch
+    import torch.nn.functional as F
+    from ured_hip import group
+    Bn = g.shape[0]
+    raw = net.fc3(F.relu(net.fc2(F.relu(net.fc1(g))))).view(Bn, 3, -1)
+    pts = torch.cat((torch.cat((raw, raw.new_zeros(Bn, 1, raw.shape[2])), 1), torch.cat((pin, pin.new_ones(Bn, 1, pin.shape[2])), 1)), 2)
+    feat = F.relu(F.conv1d(encoder_torch(net.encoder, pts), net.conv_cup1.weight, net.conv_cup1.bias))
+    high = F.conv1d(feat, net.conv_cup2.weight, net.conv_cup2.bias)
+
+    def take(t, idx):
+        return t.gather(2, idx.unsqueeze(1).expand(-1, t.shape[1], -1))
+    cur = high
+    if cur.shape[2] > net.num_fps:
+        idx = group.fps(high.detach().transpose(1, 2).contiguous(), net.num_fps,
+                        start=torch.zeros(Bn, dtype=torch.int32, device=g.device)).long()
+        cur, feat = take(cur, idx), take(feat, idx)
+    if cur.shape[2] > net.num_coarse:
+        sc = F.softplus(net.conv_s3(F.relu(net.conv_s2(F.relu(net.conv_s1(feat))))))
+        idx = sc.topk(net.num_coarse, dim=2)[1].view(Bn, -1)
+        cur, feat = take(cur, idx), take(feat, idx)
+    fine = fold_tail_torch(net, feat, g) + cur.repeat_interleave(net.expansion2.step_ratio, dim=2)
+    return raw, high, cur, fine
 
 
 # ---------------- timing ----------------
@@ -225,6 +283,40 @@ def run_leg(leg, B, iters, rounds):
             res["max_abs_diff"] = float((V.UnpoolFn.apply(feat2, idx, w, skip) - base()).abs().max())
         step = stepper([feat2, skip], go)
         fns = {"hip": lambda: step(lambda: V.UnpoolFn.apply(feat2, idx, w, skip)), "torch": lambda: step(base)}
+    elif i == 4:
+        net = M.MSAP_SKN_decoder(DEC["num_coarse_raw"], DEC["num_fps"], DEC["num_coarse"], DEC["num_fine"], [1, 1, 1, 1], [KNN], PK,
+                                 points_label=True, local_folding=True).to(dev).eval()
+        nc = DEC["num_coarse"]
+        feat = torch.randn(B, 64, nc, generator=g).to(dev).requires_grad_(True)
+        gf = torch.randn(B, 1024, generator=g).to(dev).requires_grad_(True)
+        go = torch.randn(B, 3, DEC["num_fine"], generator=g).to(dev)
+        leaves = [feat, gf] + [p for m in (net.expansion2, net.conv_f1, net.conv_f2) for p in m.parameters()]
+        step = stepper(leaves, go)
+
+        def hip():
+            return fold_tail_hip(net, feat.transpose(1, 2).reshape(B * nc, 64), gf).view(B, DEC["num_fine"], 3).transpose(1, 2)
+        with torch.no_grad():
+            res["max_abs_diff"] = float((hip() - fold_tail_torch(net, feat, gf)).abs().max())
+        fns = {"hip": lambda: step(hip), "torch": lambda: step(lambda: fold_tail_torch(net, feat, gf))}
+    elif i == 5:
+        net = M.MSAP_SKN_decoder(DEC["num_coarse_raw"], DEC["num_fps"], DEC["num_coarse"], DEC["num_fine"], [1, 1, 1, 1], [KNN], PK,
+                                 points_label=True, local_folding=True).to(dev).eval()
+        gf = torch.randn(B, 1024, generator=g).to(dev).requires_grad_(True)
+        pin = (torch.rand(B, 3, DEC["n"], generator=g) * 2 - 1).to(dev).requires_grad_(True)
+        leaves = list(net.parameters()) + [gf, pin]
+        gos = None
+
+        def step(fwd):
+            for t in leaves:
+                t.grad = None
+            outs = fwd()
+            torch.autograd.backward(outs, gos)
+        with torch.no_grad():
+            a, b = net(gf, pin), decoder_torch(net, gf, pin)
+            gos = [torch.randn(o.shape, generator=g).to(dev) for o in a]
+            res["max_abs_diff"] = float((a[0] - b[0]).abs().max())              # coarse_raw: before any search or selection
+            res["coarse_high_max_abs_diff"] = float((a[1] - b[1]).abs().max())  # after the encoder's two kNN versions
+        fns = {"hip": lambda: step(lambda: net(gf, pin)), "torch": lambda: step(lambda: decoder_torch(net, gf, pin))}
     else:
         net = M.SA_SKN_Res_encoder(CIN, [KNN], PK, 64, [1, 1, 1, 1], PTS).to(dev).eval()
         feats = torch.cat((pts.transpose(1, 2), torch.randn(B, CIN - 3, N, generator=g).to(dev)), 1).requires_grad_(True)
