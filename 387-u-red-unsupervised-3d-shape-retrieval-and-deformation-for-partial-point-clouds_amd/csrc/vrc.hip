@@ -38,6 +38,11 @@
 //   scheme of ured_vrc_sa_bwd.
 // ured_vrc_ef_max_fwd / _bwd   the max over the k slots of conv3's rows, with the winning slot.
 // ured_vrc_fold_fwd / _bwd     max(U[n] + T[s], 0) over the r grid points of every coarse point.
+// Model's variational part (models/vrcnet.py:430-501):
+// ured_vrc_latent_fwd / _bwd   softplus, the reparameterised samples of posterior and prior stacked as the
+//   generator's [2B][Z] input, and the two KL terms in torch's kl_divergence form; one launch each way.
+// ured_vrc_gauss_fwd / _bwd    compute_kernel's exp(-mean_d((x_i - y_j)^2) / Z) from direct differences, one
+//   wave per pair; the backward sums over the other set's rows in ascending order.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #define URED_DBG_FILE 18
@@ -737,8 +742,162 @@ __global__ __launch_bounds__(VRC_T) void fold_bwd_t_kernel(const float* __restri
     ws[(long long)blockIdx.x * rc + col] = acc;
 }
 
+// ---- Model's latent heads (models/vrcnet.py:457-501) ----
+// torch's softplus (beta 1, threshold 20) and its derivative z / (z + 1), z = exp(x); 1 above the threshold
+__device__ __forceinline__ float softplus20(float x) { return x > 20.f ? x : log1pf(expf(x)); }
+__device__ __forceinline__ float softplus20_grad(float x) {
+    if (x > 20.f) return 1.f;
+    const float z = expf(x);
+    return z / (z + 1.f);
+}
+
+// KL(N(mp, sp) || N(mq, sq)) in the form of torch's kl_divergence: r = (sp / sq)^2, t = ((mp - mq) / sq)^2
+__device__ __forceinline__ float kl_normal(float mp, float sp, float mq, float sq, float& r, float& t) {
+    const float a = sp / sq, d = (mp - mq) / sq;
+    r = a * a;
+    t = d * d;
+    return 0.5f * (((r + t) - 1.f) - logf(r));
+}
+
+// thread = one (b, d) of [B][Z]; o rows are [mu (Z) | raw scale (Z)]
+__global__ __launch_bounds__(VRC_T) void latent_fwd_kernel(const float* __restrict__ oq, const float* __restrict__ op,
+                                                           const float* __restrict__ eq, const float* __restrict__ ep, int Z,
+                                                           long long total, float* __restrict__ z, float* __restrict__ kl_rec,
+                                                           float* __restrict__ kl_g) {
+    const long long i = (long long)blockIdx.x * VRC_T + threadIdx.x;
+    if (i >= total) return;                           // total = B * Z
+    const long long b = i / Z;
+    const int d = (int)(i - b * Z);
+    const long long at = b * 2 * Z + d;
+    URED_DBG_CHECK(at + Z < 2 * total);
+    const float mq = oq[at], sq = softplus20(oq[at + Z]);
+    z[i] = mq + sq * eq[i];
+    if (op) {
+        const float mp = op[at], sp = softplus20(op[at + Z]);
+        z[total + i] = mp + sp * ep[i];
+        float r, t;
+        kl_rec[i] = kl_normal(0.f, 1.f, mp, sp, r, t);
+        kl_g[i] = kl_normal(mp, sp, mq, sq, r, t);
+    }
+}
+
+// d kl / d mq = -((mp - mq) / sq) / sq, d kl / d sq = -((r - 1) + t) / sq; kl_g reaches the posterior only, kl_rec the
+// prior only; absent cotangents (null) count as zero; every element of d_oq (and d_op) is written
+__global__ __launch_bounds__(VRC_T) void latent_bwd_kernel(const float* __restrict__ oq, const float* __restrict__ op,
+                                                           const float* __restrict__ eq, const float* __restrict__ ep,
+                                                           const float* __restrict__ dz, const float* __restrict__ dkr,
+                                                           const float* __restrict__ dkg, int Z, long long total,
+                                                           float* __restrict__ d_oq, float* __restrict__ d_op) {
+    const long long i = (long long)blockIdx.x * VRC_T + threadIdx.x;
+    if (i >= total) return;
+    const long long b = i / Z;
+    const int d = (int)(i - b * Z);
+    const long long at = b * 2 * Z + d;
+    URED_DBG_CHECK(at + Z < 2 * total);
+    const float mq = oq[at], xq = oq[at + Z], sq = softplus20(xq);
+    float dmq = 0.f, dsq = 0.f;
+    if (dz) {
+        const float g = dz[i];
+        dmq = g;
+        dsq = g * eq[i];
+    }
+    if (op) {
+        const float mp = op[at], xp = op[at + Z], sp = softplus20(xp);
+        float dmp = 0.f, dsp = 0.f;
+        if (dz) {
+            const float g = dz[total + i];
+            dmp = g;
+            dsp = g * ep[i];
+        }
+        if (dkr) {
+            float r, t;
+            kl_normal(0.f, 1.f, mp, sp, r, t);
+            const float g = dkr[i];
+            dmp += g * ((mp / sp) / sp);
+            dsp += g * (-((r - 1.f) + t) / sp);
+        }
+        if (dkg) {
+            float r, t;
+            kl_normal(mp, sp, mq, sq, r, t);
+            const float g = dkg[i];
+            dmq += g * (-((mp - mq) / sq) / sq);
+            dsq += g * (-((r - 1.f) + t) / sq);
+        }
+        d_op[at] = dmp;
+        d_op[at + Z] = dsp * softplus20_grad(xp);
+    }
+    d_oq[at] = dmq;
+    d_oq[at + Z] = dsq * softplus20_grad(xq);
+}
+
+// ---- compute_kernel (models/vrcnet.py:430-437) ----
+// One wave per pair (i, j): lane l sums (x[i][d] - y[j][d])^2 over d = l, l + 64, .. ascending, the 64 lane
+// sums meet in wave_sum's butterfly; K = exp(-(sum / Z) / Z). Equal rows give exp(-0) = 1 exactly.
+__global__ __launch_bounds__(VRC_T) void gauss_fwd_kernel(const float* __restrict__ x, const float* __restrict__ y, int n, int m,
+                                                          int Z, float* __restrict__ K) {
+    const long long p = (long long)blockIdx.x * VRC_W + (threadIdx.x >> 6);
+    const int ln = threadIdx.x & 63;
+    if (p >= (long long)n * m) return;                // whole waves leave; no barrier below
+    const int i = (int)(p / m), j = (int)(p - (long long)i * m);
+    URED_DBG_CHECK(i < n && j < m);
+    const float* xr = x + (size_t)i * Z;
+    const float* yr = y + (size_t)j * Z;
+    float acc = 0.f;
+    for (int d = ln; d < Z; d += 64) {
+        const float df = xr[d] - yr[d];
+        acc += df * df;
+    }
+    acc = wave_sum(acc);
+    if (ln == 0) K[p] = expf(-(acc / (float)Z) / (float)Z);
+}
+
+// thread = one (row, d) of dx [n][Z] then of dy [m][Z]:
+//   dx[i][d] = sum_j (dK[i][j] K[i][j] * -coef) * (x[i][d] - y[j][d]), j ascending
+//   dy[j][d] = sum_i (dK[i][j] K[i][j] *  coef) * (x[i][d] - y[j][d]), i ascending;  coef = 2 / Z^2
+__global__ __launch_bounds__(VRC_T) void gauss_bwd_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                          const float* __restrict__ K, const float* __restrict__ dK, int n, int m,
+                                                          int Z, float coef, float* __restrict__ dx, float* __restrict__ dy) {
+    const long long e = (long long)blockIdx.x * VRC_T + threadIdx.x;
+    const long long nx = (long long)n * Z, ny = (long long)m * Z;
+    if (e >= nx + ny) return;
+    float acc = 0.f;
+    if (e < nx) {
+        const int i = (int)(e / Z), d = (int)(e - (long long)i * Z);
+        const float xv = x[e];
+        for (int j = 0; j < m; ++j) {
+            const size_t at = (size_t)i * m + j;
+            acc += ((dK[at] * K[at]) * -coef) * (xv - y[(size_t)j * Z + d]);
+        }
+        dx[e] = acc;
+    } else {
+        const long long f = e - nx;
+        const int j = (int)(f / Z), d = (int)(f - (long long)j * Z);
+        URED_DBG_CHECK(j < m && d < Z);
+        const float yv = y[f];
+        for (int i = 0; i < n; ++i) {
+            const size_t at = (size_t)i * m + j;
+            acc += ((dK[at] * K[at]) * coef) * (x[(size_t)i * Z + d] - yv);
+        }
+        dy[f] = acc;
+    }
+}
+
 inline unsigned blocks_for(long long n) { return (unsigned)((n + VRC_T - 1) / VRC_T); }
 constexpr long long LIM = 1ll << 31;
+
+int latent_check(const char* who, int B, int Z) {
+    URED_REQUIRE(Z >= 1 && Z <= URED_VRC_ZMAX, "%s: Z %d outside [1, %d]", who, Z, URED_VRC_ZMAX);
+    URED_REQUIRE(B >= 1 && B <= 65535, "%s: B %d outside [1, 65535]", who, B);
+    URED_REQUIRE(2ll * B * Z < LIM, "%s: 2 * B * Z = %lld exceeds 2^31 - 1", who, 2ll * B * Z);
+    return 0;
+}
+
+int gauss_check(const char* who, int n, int m, int Z) {
+    URED_REQUIRE(n >= 1 && n <= URED_VRC_GAUSS_MAX && m >= 1 && m <= URED_VRC_GAUSS_MAX, "%s: n %d or m %d outside [1, %d]",
+                 who, n, m, URED_VRC_GAUSS_MAX);
+    URED_REQUIRE(Z >= 1 && Z <= URED_VRC_ZMAX, "%s: Z %d outside [1, %d]", who, Z, URED_VRC_ZMAX);
+    return 0;
+}
 
 int ef_edge_check(const char* who, int B, int N, int k, int W) {
     URED_REQUIRE(B >= 0 && N >= 1, "%s: bad sizes B=%d N=%d", who, B, N);
@@ -1047,6 +1206,53 @@ int ured_vrc_fold_bwd(const float* g, const float* out, int B, int N, int r, int
     hipLaunchKernelGGL(fold_bwd_t_kernel, dim3((unsigned)nchunks, (unsigned)((rc + VRC_T - 1) / VRC_T)), dim3(VRC_T), 0, st, g,
                        out, rows, (int)rc, chunk, ws);
     return ured::launch_status("ured_vrc_fold_bwd");
+}
+
+int ured_vrc_latent_fwd(const float* oq, const float* op, const float* eps_q, const float* eps_p, int B, int Z, float* z,
+                        float* kl_rec, float* kl_g, void* stream) {
+    ured::clear_error();
+    if (const int rc = latent_check("ured_vrc_latent_fwd", B, Z)) return rc;
+    URED_REQUIRE(oq && eps_q && z, "ured_vrc_latent_fwd: null pointer");
+    URED_REQUIRE(!op || (eps_p && kl_rec && kl_g), "ured_vrc_latent_fwd: the training form needs eps_p, kl_rec and kl_g");
+    const long long total = (long long)B * Z;
+    hipLaunchKernelGGL(latent_fwd_kernel, dim3(blocks_for(total)), dim3(VRC_T), 0, (hipStream_t)stream, oq, op, eps_q, eps_p, Z,
+                       total, z, kl_rec, kl_g);
+    return ured::launch_status("ured_vrc_latent_fwd");
+}
+
+int ured_vrc_latent_bwd(const float* oq, const float* op, const float* eps_q, const float* eps_p, const float* dz,
+                        const float* d_kl_rec, const float* d_kl_g, int B, int Z, float* d_oq, float* d_op, void* stream) {
+    ured::clear_error();
+    if (const int rc = latent_check("ured_vrc_latent_bwd", B, Z)) return rc;
+    URED_REQUIRE(oq && eps_q && d_oq, "ured_vrc_latent_bwd: null pointer");
+    URED_REQUIRE(!op || (eps_p && d_op), "ured_vrc_latent_bwd: the training form needs eps_p and d_op");
+    URED_REQUIRE(op || (!d_kl_rec && !d_kl_g), "ured_vrc_latent_bwd: the evaluation form has no KL cotangents");
+    const long long total = (long long)B * Z;
+    hipLaunchKernelGGL(latent_bwd_kernel, dim3(blocks_for(total)), dim3(VRC_T), 0, (hipStream_t)stream, oq, op, eps_q, eps_p, dz,
+                       d_kl_rec, d_kl_g, Z, total, d_oq, d_op);
+    return ured::launch_status("ured_vrc_latent_bwd");
+}
+
+int ured_vrc_gauss_fwd(const float* x, const float* y, int n, int m, int Z, float* K, void* stream) {
+    ured::clear_error();
+    if (const int rc = gauss_check("ured_vrc_gauss_fwd", n, m, Z)) return rc;
+    URED_REQUIRE(x && y && K, "ured_vrc_gauss_fwd: null pointer");
+    const long long pairs = (long long)n * m;
+    hipLaunchKernelGGL(gauss_fwd_kernel, dim3((unsigned)((pairs + VRC_W - 1) / VRC_W)), dim3(VRC_T), 0, (hipStream_t)stream, x, y,
+                       n, m, Z, K);
+    return ured::launch_status("ured_vrc_gauss_fwd");
+}
+
+int ured_vrc_gauss_bwd(const float* x, const float* y, const float* K, const float* dK, int n, int m, int Z, float* dx,
+                       float* dy, void* stream) {
+    ured::clear_error();
+    if (const int rc = gauss_check("ured_vrc_gauss_bwd", n, m, Z)) return rc;
+    URED_REQUIRE(x && y && K && dK && dx && dy, "ured_vrc_gauss_bwd: null pointer");
+    const long long total = ((long long)n + m) * Z;
+    const float coef = 2.f / ((float)Z * (float)Z);
+    hipLaunchKernelGGL(gauss_bwd_kernel, dim3(blocks_for(total)), dim3(VRC_T), 0, (hipStream_t)stream, x, y, K, dK, n, m, Z, coef,
+                       dx, dy);
+    return ured::launch_status("ured_vrc_gauss_bwd");
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
-"""VRCNet's self-attention encoder and decoder (Density_aware_Chamfer_Distance/models/vrcnet.py:15-403) on
-the HIP Functions of ured_hip.vrc: SA_module, SK_SA_module, SKN_Res_unit, SA_SKN_Res_encoder,
-Linear_ResBlock, Folding and MSAP_SKN_decoder.
+"""VRCNet (Density_aware_Chamfer_Distance/models/vrcnet.py:15-539) on the HIP Functions of ured_hip.vrc:
+SA_module, SK_SA_module, SKN_Res_unit, SA_SKN_Res_encoder, Linear_ResBlock, Folding, MSAP_SKN_decoder and
+Model.
 
 Same names, constructor arguments, parameter names and shapes as the reference (the nn.Conv2d /
 nn.Linear modules only hold the parameters, Conv2d weights stay [out, in, 1, 1]), so a reference
@@ -21,22 +21,46 @@ chamfer3D/model_utils.py. Folding never builds its [B, G + C + 2, N r] input (ro
 grid table, FoldFn); the decoder's fully connected and 1x1 layers are linear_rows, FPS on the predicted
 points is ured_hip.group.fps from index 0, the gathers are GroupFn (ordered backward), the score ranking is
 a stable descending sort (lowest index first on a tie; the reference's topk leaves ties open) and
-F.softplus stays torch's own. Only Model (the VAE heads, rsample, the KLD / MMD terms, the loss mix)
-remains unbuilt.
+F.softplus on the scores stays torch's own.
+
+Model (vrcnet.py:406-539): PCN_encoder on [x; y], the posterior / prior heads, LatentFn (softplus, the
+reparameterised samples stacked as the generator's [2B, Z] input, both KL terms: one launch each way),
+GaussKernelFn for compute_kernel / mmd_loss, one decoder call on the doubled batch and the four-head loss
+mix. forward returns what the reference returns. Decided here where the reference leaves a gap or fails:
+  - `noise` (keyword only): the standard-normal draws as a sequence of [B, size_z] tensors, consumed in the
+    reference's order (training: eps_q, eps_p, then for MMD eps_m, eps_q', eps_p', eps_pfix; evaluation:
+    one). None draws them with torch.randn on the input's device.
+  - `alpha=None` in training raises ValueError (the reference fails on a NoneType product).
+  - `mmd_loss2` exists nowhere in the reference, so its distribution_loss='MMD' branch raises
+    AttributeError (every shipped cfg uses KLD); here both MMD terms use mmd_loss.
+  - loss='emd': loss4 is the per-cloud emd [2B], as in models/pcn.py; so is the evaluation dict's 'emd'.
+  - torch.distributions.Normal's argument validation is not reproduced: a softplus that underflows to 0
+    gives an infinite KL here where the reference raises.
+  - the reference's Linear_ResBlock rectifies its input in place, so after the heads have run the code that
+    goes to the decoder is relu(feat_x) + generator(z) (its in-place ReLU on a chunk of the encoder's output
+    is an error in current torch; the rectified value is what it computed where it ran). Stated here with an
+    explicit ReLU; the caller's tensors are left as they are.
+  - shared fourth head: when the decoder returns `fine` as the very same cloud as `coarse` (num_coarse ==
+    num_fine, the shape of vrc_dcd.yaml and vrc_plus.yaml) and loss is cd or dcd, heads 3 and 4 are one
+    computation: one calc_cd / calc_dcd call, used as (1 + alpha) * loss.mean(); loss4 is that call's.
+  - `pts_num` (getattr(args, "pts_num", None)) is handed to the decoder, for test sizes.
 
 Setting `net.decisions = {}` on a module makes its next forward export the discrete decisions: the
 kNN / FPS / pooling-neighbour / three-NN indices of the encoder, the pre-activation of every ReLU
-('pre': name -> tensor, the mask is pre > 0) and the pool slots.
+('pre': name -> tensor, the mask is pre > 0) and the pool slots; on Model, 'y_fps' (the FPS indices that
+pick y from gt), 'feat' (the code handed to the decoder), 'dl_rec' / 'dl_g' and 'dec' (the decoder's own record).
 """
 import math
 
 import torch
 import torch.nn as nn
 
-from chamfer3D.model_utils import EF_expansion, edge_preserve_sampling_rows, gen_grid_up, knn, three_nn_upsampling
+from chamfer3D.model_utils import (EF_expansion, calc_cd, calc_dcd, calc_emd, edge_preserve_sampling_rows, gen_grid_up, knn,
+                                   three_nn_upsampling)
+from models.pcn import PCN_encoder
 from ured_hip.group import GroupFn, fps
-from ured_hip.vrc import (CMAX, CenterFn, FoldFn, MaxRowsFn, MMAX, ReluFn, RMAX, SaFn, SkMeanFn, SkMixFn, UnpoolFn,
-                          linear_rows, sa_check)
+from ured_hip.vrc import (CMAX, CenterFn, FoldFn, GaussKernelFn, LatentFn, MaxRowsFn, MMAX, ReluFn, RMAX, SaFn, SkMeanFn,
+                          SkMixFn, UnpoolFn, latent_check, linear_rows, sa_check)
 
 
 def _w2(conv):
@@ -472,5 +496,140 @@ class MSAP_SKN_decoder(nn.Module):
             if N != self.num_fine:
                 raise ValueError(f"MSAP_SKN_decoder: {N} coarse points exceed num_fine {self.num_fine}")
             fine, n_fine = coarse, N
-        return (coarse_raw, _unrows(high, B, high.shape[0] // B, four=False), _unrows(coarse, B, N, four=False),
-                _unrows(fine, B, n_fine, four=False))
+        coarse_out = _unrows(coarse, B, N, four=False)
+        fine_out = coarse_out if fine is coarse else _unrows(fine, B, n_fine, four=False)      # one cloud, one object
+        return coarse_raw, _unrows(high, B, high.shape[0] // B, four=False), coarse_out, fine_out
+
+
+class Model(nn.Module):
+    """VRCNet: see the module docstring for the contract and for what is decided here."""
+
+    def __init__(self, args, size_z=128, global_feature_size=1024):
+        super().__init__()
+        layers = [int(i) for i in args.layers.split(',')]
+        knn_list = [int(i) for i in args.knn_list.split(',')]
+        latent_check("Model", 1, size_z)
+        self.size_z = size_z
+        self.distribution_loss = args.distribution_loss
+        self.train_loss = args.loss
+        self.loss_opts = args.loss_opts
+        self.eval_emd = args.eval_emd
+        self.encoder = PCN_encoder(output_size=global_feature_size)
+        self.posterior_infer1 = Linear_ResBlock(input_size=global_feature_size, output_size=global_feature_size)
+        self.posterior_infer2 = Linear_ResBlock(input_size=global_feature_size, output_size=size_z * 2)
+        self.prior_infer = Linear_ResBlock(input_size=global_feature_size, output_size=size_z * 2)
+        self.generator = Linear_ResBlock(input_size=size_z, output_size=global_feature_size)
+        self.decoder = MSAP_SKN_decoder(num_fps=args.num_fps, num_fine=args.num_points, num_coarse=args.num_coarse,
+                                        num_coarse_raw=args.num_coarse_raw, layers=layers, knn_list=knn_list, pk=args.pk,
+                                        local_folding=args.local_folding, points_label=args.points_label,
+                                        pts_num=getattr(args, "pts_num", None))
+
+    def compute_kernel(self, x, y):
+        return GaussKernelFn.apply(x, y)
+
+    def mmd_loss(self, x, y):
+        return self.compute_kernel(x, x).mean() + self.compute_kernel(y, y).mean() - 2 * self.compute_kernel(x, y).mean()
+
+    def _draws(self, noise, B, like):
+        """-> a function returning the next standard-normal [B, size_z] tensor."""
+        Z = self.size_z
+        if noise is None:
+            return lambda: torch.randn(B, Z, device=like.device)
+        left = list(noise)
+
+        def draw():
+            if not left:
+                raise ValueError("Model.forward: noise holds fewer tensors than the forward draws")
+            t = left.pop(0)
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (B, Z):
+                raise ValueError(f"Model.forward: every noise tensor must be float32 [{B}, {Z}]")
+            return t.to(like.device)
+        return draw
+
+    def forward(self, x, gt, is_training=True, mean_feature=None, alpha=None, test_emd=True, *, noise=None):
+        if x.dim() != 3 or x.shape[1] != 3:
+            raise ValueError(f"Model.forward: x must be [B, 3, n], got {tuple(x.shape)}")
+        if gt.dim() != 3 or gt.shape[0] != x.shape[0] or gt.shape[2] != 3:
+            raise ValueError(f"Model.forward: gt must be [{x.shape[0]}, m, 3], got {tuple(gt.shape)}")
+        if is_training and alpha is None:
+            raise ValueError("Model.forward: training needs alpha (the weight of the fine loss)")
+        B, _, num_input = x.shape
+        rec = getattr(self, "decisions", None)
+        rec = rec if isinstance(rec, dict) else None
+        draw = self._draws(noise, B, x)
+        if is_training:
+            gt = gt.contiguous()
+            y_idx = fps(gt.detach(), num_input, start=torch.zeros(B, dtype=torch.int32, device=gt.device))
+            if rec is not None:
+                rec["y_fps"] = y_idx
+            y = GroupFn.apply(None, None, gt, y_idx.unsqueeze(2).contiguous()).view(B, num_input, 3).transpose(1, 2)
+            feat = self.encoder(torch.cat((x, y), 0).contiguous())
+            feat_x, feat_y = ReluFn.apply(feat[:B]), feat[B:]
+            o_x = self.posterior_infer2(self.posterior_infer1(feat_x))
+            o_y = self.prior_infer(feat_y)
+            z, kl_rec, kl_g = LatentFn.apply(o_x, o_y, draw(), draw())
+            feat = feat_x.repeat(2, 1) + self.generator(z)
+            gt = gt.repeat(2, 1, 1)
+            x = x.repeat(2, 1, 1)
+        else:
+            feat = ReluFn.apply(self.encoder(x.contiguous()))
+            o_x = self.posterior_infer2(self.posterior_infer1(feat))
+            z = LatentFn.apply(o_x, None, draw(), None)[0]
+            feat = feat + self.generator(z)
+        if rec is not None:
+            rec["feat"] = feat
+            self.decoder.decisions = {}
+        coarse_raw, coarse_high, coarse, fine = self.decoder(feat, x)
+        if rec is not None:
+            rec["dec"] = self.decoder.decisions
+            del self.decoder.decisions
+        shared = fine is coarse
+        coarse_raw = coarse_raw.transpose(1, 2).contiguous()
+        coarse_high = coarse_high.transpose(1, 2).contiguous()
+        coarse = coarse.transpose(1, 2).contiguous()
+        fine = coarse if shared else fine.transpose(1, 2).contiguous()
+        if not is_training:
+            if self.eval_emd and test_emd:
+                emd, _ = calc_emd(fine, gt, eps=0.004, iterations=3000)
+            else:
+                emd = torch.ones(1, device=fine.device)
+            _, cd_t, f1 = calc_cd(fine, gt, calc_f1=True)
+            dcd, _, _ = calc_dcd(fine, gt)
+            return {'out1': coarse_raw, 'out2': fine, 'emd': emd, 'dcd': dcd, 'cd_t': cd_t, 'f1': f1}
+        if self.distribution_loss == 'MMD':
+            z_m = draw()                                                          # N(0, 1).rsample()
+            z2 = LatentFn.apply(o_x, o_y, draw(), draw())[0]
+            z_p_fix = LatentFn.apply(o_y.detach(), None, draw(), None)[0]
+            dl_rec = self.mmd_loss(z_m, z2[B:])
+            dl_g = self.mmd_loss(z2[:B], z_p_fix)
+        elif self.distribution_loss == 'KLD':
+            dl_rec, dl_g = kl_rec, kl_g
+        else:
+            raise NotImplementedError('Distribution loss is either MMD or KLD')
+        if rec is not None:
+            rec["dl_rec"], rec["dl_g"] = dl_rec, dl_g
+        if self.train_loss == 'cd':
+            def head(cloud, first=False):
+                return calc_cd(cloud, gt)[0]
+        elif self.train_loss == 'dcd':
+            t_alpha, n_lambda = self.loss_opts["alpha"], self.loss_opts["lambda"]
+
+            def head(cloud, first=False):
+                return calc_dcd(cloud, gt, alpha=t_alpha * 2 if first else t_alpha, n_lambda=n_lambda)[0]
+        elif self.train_loss == 'emd':
+            def head(cloud, first=False):
+                return calc_cd(cloud, gt)[0]
+            shared = False
+        else:
+            raise NotImplementedError(self.train_loss)
+        loss1, loss2 = head(coarse_raw, True), head(coarse_high)
+        total_train_loss = loss1.mean() * 10 + loss2.mean() * 0.5
+        if shared:
+            loss4 = head(coarse)
+            total_train_loss = total_train_loss + loss4.mean() * (1 + alpha)
+        else:
+            loss3 = head(coarse)
+            loss4 = calc_emd(fine, gt)[0] if self.train_loss == 'emd' else head(fine)
+            total_train_loss = total_train_loss + loss3.mean() + loss4.mean() * alpha
+        total_train_loss = total_train_loss + (dl_rec.mean() + dl_g.mean()) * 20
+        return fine, loss4, total_train_loss, None

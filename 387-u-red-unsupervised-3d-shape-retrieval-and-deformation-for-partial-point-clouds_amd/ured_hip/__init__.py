@@ -18,7 +18,9 @@
   dcd      density-aware chamfer as a training loss: DcdLossFn / dcd_loss (one launch each way after the NN)
   pcn      the PCN completion network: PcnEncoderFn, PcnDecoderFn and the fold / pool / ReLU kernels
   vrc      VRCNet's self-attention encoder and decoder: SaFn, SkMeanFn, SkMixFn, EdgePoolFn, UnpoolFn,
-           LinearRowsFn, and the expansion units' EfEdgeFn, EfMaxFn, FoldFn, CenterFn
+           LinearRowsFn, the expansion units' EfEdgeFn, EfMaxFn, FoldFn, CenterFn, and Model's LatentFn (latent
+           heads, KL terms) and GaussKernelFn (the MMD kernel matrix), both also exported here
   losshead the step's loss head (chamfer families, contrastive, residual, reconstruction, weighted sum)
 """
 from . import _lib, attn, dcd, gcn, group, interp, kernels, losshead, nn, node, occ, ops, optim, pcn, syncbn, vn, vrc  # noqa: F401
+from .vrc import GaussKernelFn, LatentFn  # noqa: E402,F401

@@ -15,6 +15,9 @@ EfEdgeFn    the per-edge rows of EF_expansion, relu((G +) centre[n] + neighbour[
             halves of conv1 / conv2; no [B, 2C, k, N] or [B, O + 2C, k, N] tensor exists.
 EfMaxFn     the max over the k slots of conv3's rows (lowest j on a tie), with the winning slot.
 FoldFn      relu(U[n] + T[s]) over the r grid points of every coarse point (Folding).
+LatentFn    Model's latent heads: softplus, the reparameterised samples stacked as the generator's [2B, Z]
+            input, KL(N(0,1) || prior) and KL(prior || posterior); one launch each way, nothing saved but the inputs.
+GaussKernelFn  compute_kernel's exp(-mean_d((x_i - y_j)^2) / Z) without the two [n, m, Z] tiled tensors.
 LinearRowsFn / ReluFn / MaxRowsFn  the GEMM layers between them (bias, ReLU prologue, per-cloud row
             bias), the ReLU and the max over a cloud's points.
 Arguments are validated before any device work; a tensor off the device raises (no CPU path).
@@ -47,11 +50,16 @@ _lib.register({
     "ured_vrc_ef_max_bwd": [_P, _P, _I, _I, _I, _I, _I, _P, _P],
     "ured_vrc_fold_fwd": [_P, _P, _I, _I, _I, _I, _P, _P],
     "ured_vrc_fold_bwd": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
+    "ured_vrc_latent_fwd": [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P],
+    "ured_vrc_latent_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P],
+    "ured_vrc_gauss_fwd": [_P, _P, _I, _I, _I, _P, _P],
+    "ured_vrc_gauss_bwd": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P],
 })
 
 KMAX, RELMAX, MIDMAX, MSMAX, MMAX, PKMAX = 32, 32, 128, 16, 4, 32      # URED_VRC_* (include/ured_hip.h)
 CMAX = 512                          # URED_VRC_CMAX: the widest SA_module / EF_expansion input
 OMAX, RMAX = 256, 16                # URED_VRC_OMAX, URED_VRC_RMAX: EF_expansion's output_size and step_ratio
+ZMAX, GAUSS_MAX = 4096, 4096         # URED_VRC_ZMAX, URED_VRC_GAUSS_MAX: the latent width, the rows of a Gaussian kernel
 MAX_B = 65535
 _LIM = 1 << 31
 WA_MIN_CHUNK, WA_CHUNKS = 32, 1024  # points per workgroup of the dWa partials: at least 32, about 1024 workgroups
@@ -445,6 +453,112 @@ class FoldFn(Function):
         ws = torch.empty(nch, r * Co, device=g.device)
         _lib.call("ured_vrc_fold_bwd", _p(g), _p(out), 1, R, r, Co, chunk, _p(dU), _p(ws), _lib.stream_of(g))
         return dU, K.colsum(ws).view(r, Co)
+
+
+def latent_check(who, B, Z):
+    """The limits of the latent-head kernels."""
+    if not 1 <= Z <= ZMAX:
+        raise ValueError(f"{who}: Z {Z} outside [1, {ZMAX}]")
+    if B < 1 or B > MAX_B:
+        raise ValueError(f"{who}: B {B} outside [1, {MAX_B}]")
+    if 2 * B * Z >= _LIM:
+        raise ValueError(f"{who}: 2 * B * Z must stay below 2^31")
+
+
+class LatentFn(Function):
+    """(oq [B, 2Z], op [B, 2Z], eps_q [B, Z], eps_p [B, Z]) -> (z [2B, Z], kl_rec [B, Z], kl_g [B, Z]); with
+    op = eps_p = None (evaluation) -> z [B, Z], and kl_rec / kl_g are None. mu = o[:, :Z], s = softplus(o[:, Z:]);
+    z = [mu_q + s_q eps_q; mu_p + s_p eps_p], kl_rec = KL(N(0,1) || N(mu_p, s_p)), kl_g = KL(N(mu_p, s_p) ||
+    N(mu_q, s_q)) with the prior detached. eps takes no gradient."""
+
+    @staticmethod
+    def forward(ctx, oq, op, eps_q, eps_p):
+        who = "LatentFn"
+        _f32(who, "oq", oq, (None, None))
+        B, W = oq.shape
+        if W < 2 or W % 2:
+            raise ValueError(f"{who}: oq has {W} columns, expected [mu | scale] halves")
+        Z = W // 2
+        latent_check(who, B, Z)
+        _f32(who, "eps_q", eps_q, (B, Z))
+        if (op is None) != (eps_p is None):
+            raise ValueError(f"{who}: op and eps_p go together (both for training, neither for evaluation)")
+        train = op is not None
+        if train:
+            _f32(who, "op", op, (B, 2 * Z))
+            _f32(who, "eps_p", eps_p, (B, Z))
+        _lib.require_device(oq, op, eps_q, eps_p)
+        oq, eps_q = oq.contiguous(), eps_q.contiguous()
+        dev = oq.device
+        kl_rec = kl_g = None
+        if train:
+            op, eps_p = op.contiguous(), eps_p.contiguous()
+            kl_rec, kl_g = torch.empty(B, Z, device=dev), torch.empty(B, Z, device=dev)
+        z = torch.empty(2 * B if train else B, Z, device=dev)
+        _lib.call("ured_vrc_latent_fwd", _p(oq), _p(op), _p(eps_q), _p(eps_p), B, Z, _p(z), _p(kl_rec), _p(kl_g),
+                  _lib.stream_of(oq))
+        ctx.set_materialize_grads(False)
+        if train:
+            ctx.save_for_backward(oq, op, eps_q, eps_p)
+        else:
+            ctx.save_for_backward(oq, eps_q)
+        ctx.dims = (B, Z, train)
+        return z, kl_rec, kl_g
+
+    @staticmethod
+    def backward(ctx, dz, dkr, dkg):
+        B, Z, train = ctx.dims
+        if train:
+            oq, op, eps_q, eps_p = ctx.saved_tensors
+        else:
+            (oq, eps_q), op, eps_p = ctx.saved_tensors, None, None
+            dkr = dkg = None
+        dz, dkr, dkg = (None if g is None else g.contiguous() for g in (dz, dkr, dkg))
+        d_oq = torch.empty_like(oq)
+        d_op = torch.empty_like(op) if train else None
+        _lib.call("ured_vrc_latent_bwd", _p(oq), _p(op), _p(eps_q), _p(eps_p), _p(dz), _p(dkr), _p(dkg), B, Z, _p(d_oq),
+                  _p(d_op), _lib.stream_of(oq))
+        return d_oq, d_op, None, None
+
+
+def gauss_check(who, n, m, Z):
+    """The limits of the Gaussian-kernel kernels."""
+    if not 1 <= n <= GAUSS_MAX or not 1 <= m <= GAUSS_MAX:
+        raise ValueError(f"{who}: n {n} or m {m} outside [1, {GAUSS_MAX}]")
+    if not 1 <= Z <= ZMAX:
+        raise ValueError(f"{who}: Z {Z} outside [1, {ZMAX}]")
+
+
+class GaussKernelFn(Function):
+    """(x [n, Z], y [m, Z]) -> K [n, m] = exp(-mean_d((x_i - y_j)^2) / Z) from direct differences (equal rows give
+    exactly 1); dx sums over j ascending, dy over i ascending. x and y may be the same tensor: autograd adds
+    the two roles' gradients."""
+
+    @staticmethod
+    def forward(ctx, x, y):
+        who = "GaussKernelFn"
+        _f32(who, "x", x, (None, None))
+        n, Z = x.shape
+        _f32(who, "y", y, (None, Z))
+        m = y.shape[0]
+        gauss_check(who, n, m, Z)
+        _lib.require_device(x, y)
+        x, y = x.contiguous(), y.contiguous()
+        K_ = torch.empty(n, m, device=x.device)
+        _lib.call("ured_vrc_gauss_fwd", _p(x), _p(y), n, m, Z, _p(K_), _lib.stream_of(x))
+        ctx.save_for_backward(x, y, K_)
+        ctx.set_materialize_grads(False)
+        return K_
+
+    @staticmethod
+    def backward(ctx, dK):
+        if dK is None:
+            return None, None
+        x, y, K_ = ctx.saved_tensors
+        dx, dy = torch.empty_like(x), torch.empty_like(y)
+        _lib.call("ured_vrc_gauss_bwd", _p(x), _p(y), _p(K_), _p(dK.contiguous()), x.shape[0], y.shape[0], x.shape[1], _p(dx),
+                  _p(dy), _lib.stream_of(x))
+        return dx, dy
 
 
 class CenterFn(Function):

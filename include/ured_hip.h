@@ -54,6 +54,9 @@
  *   ured_vrc_ef_edge_fwd / ured_vrc_ef_edge_bwd / ured_vrc_ef_max_fwd / ured_vrc_ef_max_bwd / ured_vrc_fold_fwd /
  *   ured_vrc_fold_bwd   <- the per-edge part of EF_expansion (utils/model_utils.py:137-166) and Folding's
  *                       repeat + concatenation + ReLU (models/vrcnet.py:54-86) and their autograd.
+ *   ured_vrc_latent_fwd / ured_vrc_latent_bwd / ured_vrc_gauss_fwd / ured_vrc_gauss_bwd
+ *                       <- Model's softplus, rsample, kl_divergence and compute_kernel
+ *                       (models/vrcnet.py:430-501) and their autograd.
  */
 #ifndef URED_HIP_H
 #define URED_HIP_H
@@ -66,7 +69,7 @@ extern "C" {
 #define URED_EINVAL 1001
 
 /* Library identification: returns URED_ABI_VERSION. */
-#define URED_ABI_VERSION 18  /* 18: ured_vrc_ef_edge_fwd / ured_vrc_ef_edge_bwd / ured_vrc_ef_max_fwd / ured_vrc_ef_max_bwd / ured_vrc_fold_fwd / ured_vrc_fold_bwd; 17: ured_vrc_sa_fwd / ured_vrc_sa_bwd / ured_vrc_sk_mean_fwd / ured_vrc_sk_mean_bwd / ured_vrc_sk_mix_fwd / ured_vrc_sk_mix_bwd / ured_vrc_pool_fwd / ured_vrc_pool_bwd / ured_vrc_unpool_fwd / ured_vrc_unpool_bwd; 16: ured_dcd_loss_fwd / ured_dcd_loss_bwd, ured_pcn_relu / ured_pcn_pool_bwd / ured_pcn_fold_fwd / ured_pcn_fold_bwd / ured_pcn_center_fwd / ured_pcn_center_bwd; 15:ured_vn_parts / ured_vn_knn / ured_vn_act_fwd / ured_vn_act_bwd / ured_vn_maxpool_fwd / ured_vn_maxpool_bwd / ured_vn_frame_fwd / ured_vn_frame_bwd; 14: ured_gcn_dirs / ured_gcn_conv_fwd / ured_gcn_conv_bwd / ured_gcn_conv_bwd_parts / ured_gcn_pool_fwd / ured_gcn_pool_bwd; 13: ured_interp_fwd / ured_interp_bwd; 12: ured_fps / ured_ball_query / ured_group_fwd / ured_group_bwd; 11: ured_knn_fwd / ured_knn_bwd; 10: ured_occlude; 9: ured_attn_fwd_sets / ured_attn_bwd_sets, ured_get_shape_src_fwd / _bwd; 8: ured_nn_bwd_set; 7: ured_copy_batch; 6: ured_part_rows_bwd_add; 5: node BN SyncBN fields (stats_out/stats_in, sums_out/sums_in); ured_bn_stats et al. */
+#define URED_ABI_VERSION 19  /* 19: ured_vrc_latent_fwd / ured_vrc_latent_bwd / ured_vrc_gauss_fwd / ured_vrc_gauss_bwd; 18: ured_vrc_ef_edge_fwd / ured_vrc_ef_edge_bwd / ured_vrc_ef_max_fwd / ured_vrc_ef_max_bwd / ured_vrc_fold_fwd / ured_vrc_fold_bwd; 17: ured_vrc_sa_fwd / ured_vrc_sa_bwd / ured_vrc_sk_mean_fwd / ured_vrc_sk_mean_bwd / ured_vrc_sk_mix_fwd / ured_vrc_sk_mix_bwd / ured_vrc_pool_fwd / ured_vrc_pool_bwd / ured_vrc_unpool_fwd / ured_vrc_unpool_bwd; 16: ured_dcd_loss_fwd / ured_dcd_loss_bwd, ured_pcn_relu / ured_pcn_pool_bwd / ured_pcn_fold_fwd / ured_pcn_fold_bwd / ured_pcn_center_fwd / ured_pcn_center_bwd; 15:ured_vn_parts / ured_vn_knn / ured_vn_act_fwd / ured_vn_act_bwd / ured_vn_maxpool_fwd / ured_vn_maxpool_bwd / ured_vn_frame_fwd / ured_vn_frame_bwd; 14: ured_gcn_dirs / ured_gcn_conv_fwd / ured_gcn_conv_bwd / ured_gcn_conv_bwd_parts / ured_gcn_pool_fwd / ured_gcn_pool_bwd; 13: ured_interp_fwd / ured_interp_bwd; 12: ured_fps / ured_ball_query / ured_group_fwd / ured_group_bwd; 11: ured_knn_fwd / ured_knn_bwd; 10: ured_occlude; 9: ured_attn_fwd_sets / ured_attn_bwd_sets, ured_get_shape_src_fwd / _bwd; 8: ured_nn_bwd_set; 7: ured_copy_batch; 6: ured_part_rows_bwd_add; 5: node BN SyncBN fields (stats_out/stats_in, sums_out/sums_in); ured_bn_stats et al. */
 int ured_abi_version(void);
 /* Thread-local message for the last failing call on this thread ("" if none). */
 const char* ured_last_error(void);
@@ -906,6 +909,42 @@ int ured_vrc_ef_max_bwd(const float* g, const unsigned char* slot, int B, int N,
 int ured_vrc_fold_fwd(const float* U, const float* T, int B, int N, int r, int Co, float* out, void* stream);
 int ured_vrc_fold_bwd(const float* g, const float* out, int B, int N, int r, int Co, int chunk, float* dU, float* ws,
                       void* stream);
+
+/* Model's variational part (Density_aware_Chamfer_Distance/models/vrcnet.py:430-501).
+ *
+ * ured_vrc_latent_fwd: oq [B][2Z] (the posterior head's output), op [B][2Z] (the prior head's) or null,
+ *   eps_q, eps_p [B][Z] standard-normal draws. With mu = o[:, :Z] and s = softplus(o[:, Z:]), torch's softplus
+ *   (x > 20 ? x : log1p(exp(x))):
+ *   training (op not null): z [2B][Z], rows 0..B-1 = mu_q + s_q eps_q, rows B..2B-1 = mu_p + s_p eps_p (the
+ *     generator's input, no concatenation); kl_rec [B][Z] = KL(N(0, 1) || N(mu_p, s_p)); kl_g [B][Z] =
+ *     KL(N(mu_p, s_p) || N(mu_q, s_q)); both as torch's kl_divergence, 0.5 (((r + t) - 1) - log r) with
+ *     r = (s_a / s_b)^2 and t = ((mu_a - mu_b) / s_b)^2 for KL(a || b). Equal distributions give exactly 0.
+ *   evaluation (op null): z [B][Z] = mu_q + s_q eps_q; eps_p, kl_rec and kl_g are not touched.
+ * ured_vrc_latent_bwd: the same inputs and the cotangents dz ([2B][Z], or [B][Z] in the evaluation form),
+ *   d_kl_rec, d_kl_g [B][Z], each of which may be null (= zero). Writes every element of d_oq [B][2Z] and, in the
+ *   training form, of d_op [B][2Z]. kl_g sends gradient to the posterior only (the reference detaches the prior
+ *   there), kl_rec to the prior only. The softplus derivative is z / (z + 1) with z = exp(x), and 1 above the
+ *   threshold. Nothing is saved between forward and backward but the inputs.
+ *   Limits: 1 <= Z <= URED_VRC_ZMAX, 1 <= B <= 65535, 2 B Z < 2^31.
+ *
+ * ured_vrc_gauss_fwd: x [n][Z], y [m][Z] -> K [n][m], K[i][j] = exp(-(sum_d (x[i][d] - y[j][d])^2 / Z) / Z) from
+ *   direct differences (x_i == y_j gives exactly 1). The sum over d: lane l of one wave adds d = l, l + 64, ..
+ *   ascending, then the 64 lane sums meet in a butterfly (xor 32, 16, .., 1); the order does not depend on the
+ *   launch geometry. x and y may be the same memory.
+ * ured_vrc_gauss_bwd: with w[i][j] = dK[i][j] K[i][j] and c = 2 / Z^2:
+ *   dx[i][d] = sum_j (w[i][j] * -c) (x[i][d] - y[j][d]), j ascending;
+ *   dy[j][d] = sum_i (w[i][j] *  c) (x[i][d] - y[j][d]), i ascending. Every element is written; no atomics.
+ *   When x and y are the same memory the caller adds dx and dy.
+ *   Limits: 1 <= n, m <= URED_VRC_GAUSS_MAX, 1 <= Z <= URED_VRC_ZMAX. */
+#define URED_VRC_ZMAX 4096
+#define URED_VRC_GAUSS_MAX 4096
+int ured_vrc_latent_fwd(const float* oq, const float* op, const float* eps_q, const float* eps_p, int B, int Z, float* z,
+                        float* kl_rec, float* kl_g, void* stream);
+int ured_vrc_latent_bwd(const float* oq, const float* op, const float* eps_q, const float* eps_p, const float* dz,
+                        const float* d_kl_rec, const float* d_kl_g, int B, int Z, float* d_oq, float* d_op, void* stream);
+int ured_vrc_gauss_fwd(const float* x, const float* y, int n, int m, int Z, float* K, void* stream);
+int ured_vrc_gauss_bwd(const float* x, const float* y, const float* K, const float* dK, int n, int m, int Z, float* dx,
+                       float* dy, void* stream);
 
 /* ---------------- loss head (csrc/loss.hip) ---------------- */
 /* compute_cm_loss of the deformed shape `out` [B,S,3] and of its mirror image (x -> -x,

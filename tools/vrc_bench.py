@@ -10,7 +10,10 @@ Legs: one SA unit at the first level (C 64: rel 4, mid 16) forward + backward; o
 skip channels) forward + backward; the whole encoder forward + backward; and, at the shape of cfgs/vrc.yaml
 (2048 input points, num_coarse_raw 1024, num_fps 2048, num_coarse 1024, folding, points_label): Folding +
 conv_f1 / conv_f2 (1024 -> 2048 points) forward + backward against the [B, G + C + 2, N r] tensor built in
-full, and the whole decoder forward + backward. The baselines, written out
+full, and the whole decoder forward + backward; and, at the shape of cfgs/vrc_dcd.yaml (num_coarse == num_fine, KLD,
+dcd), one training forward + backward of Model on `batch` pairs, so 2 x batch decoder clouds, against the same
+torch encoder / decoder composition with the PCN encoder, the heads, softplus / rsample / kl_divergence and the
+loss tail (dense distance matrix, min, visit counts, four heads as the reference calls them) in torch. The baselines, written out
 below: the gathered [B, C, k, N] tensor with conv2 / conv3 run on it, the attention weights repeated
 over share_planes, all kept by autograd; the gathered [B, C, S, pk] tensor and its max; three gathered
 rows times their weights; for the encoder those pieces with the module's own parameters, the
@@ -35,7 +38,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N, KNN, PK, CIN = 3072, 16, 10, 4
 PTS = [3072, 1536, 768, 384]
 LEGS = ["SA unit fwd+bwd C64 k16", "edge pool fwd+bwd 3072->1536 C64 pk10", "unpool fwd+bwd 1536->3072 128+64",
-        "encoder fwd+bwd", "Folding + conv_f1/f2 fwd+bwd 1024->2048", "decoder fwd+bwd"]
+        "encoder fwd+bwd", "Folding + conv_f1/f2 fwd+bwd 1024->2048", "decoder fwd+bwd", "model fwd+bwd vrc_dcd"]
+# the model leg: cfgs/vrc_dcd.yaml (2048 input and gt points, num_coarse == num_fine: fine is the coarse cloud; KLD, dcd 40 / 0.5)
+MODEL = dict(n=2048, n_gt=2048, num_coarse_raw=1024, num_fps=2048, num_coarse=2048, num_points=2048, size_z=128, alpha=0.5,
+             t_alpha=40, n_lambda=0.5)
 # the decoder legs: cfgs/vrc.yaml (2048 input points, num_coarse_raw 1024, num_fps 2048, num_coarse 1024, folding, points_label)
 DEC = dict(n=2048, num_coarse_raw=1024, num_fps=2048, num_coarse=1024, num_fine=2048)
 
@@ -179,8 +185,63 @@ def decoder_torch(net, g, pin):
         sc = F.softplus(net.conv_s3(F.relu(net.conv_s2(F.relu(net.conv_s1(feat))))))
         idx = sc.topk(net.num_coarse, dim=2)[1].view(Bn, -1)
         cur, feat = take(cur, idx), take(feat, idx)
+    if cur.shape[2] >= net.num_fine:                  # num_coarse == num_fine: the coarse cloud is the output
+        return raw, high, cur, cur
     fine = fold_tail_torch(net, feat, g) + cur.repeat_interleave(net.expansion2.step_ratio, dim=2)
     return raw, high, cur, fine
+
+
+def pcn_encoder_torch(e, x):
+    import torch
+    import torch.nn.functional as F
+    y2 = F.conv1d(F.relu(F.conv1d(x, e.conv1.weight, e.conv1.bias)), e.conv2.weight, e.conv2.bias)
+    h = torch.cat((y2, y2.max(2, keepdim=True)[0].expand(-1, -1, x.shape[2])), 1)
+    return F.conv1d(F.relu(F.conv1d(h, e.conv3.weight, e.conv3.bias)), e.conv4.weight, e.conv4.bias).max(2)[0]
+
+
+def lrb_torch(m, f):
+    import torch.nn.functional as F
+    f = F.relu(f)
+    return m.conv2(F.relu(m.conv1(f))) + m.conv_res(f)
+
+
+def dcd_torch(x, gt, alpha, n_lambda):
+    """calc_dcd's formulas on the dense [B, n_gt, n_x] matrix of squared distances -> the per-cloud loss."""
+    import torch
+    d = torch.cdist(gt, x) ** 2
+    (dist1, idx1), (dist2, idx2) = d.min(2), d.min(1)
+    n_x, n_gt = x.shape[1], gt.shape[1]
+    cnt1 = torch.zeros_like(idx2).scatter_add_(1, idx1, torch.ones_like(idx1))
+    cnt2 = torch.zeros_like(idx1).scatter_add_(1, idx2, torch.ones_like(idx2))
+    w1 = (cnt1.gather(1, idx1).float() ** n_lambda + 1e-6) ** (-1) * (n_gt / n_x)
+    w2 = (cnt2.gather(1, idx2).float() ** n_lambda + 1e-6) ** (-1) * (n_x / n_gt)
+    return ((1 - torch.exp(-dist1 * alpha) * w1).mean(1) + (1 - torch.exp(-dist2 * alpha) * w2).mean(1)) / 2
+
+
+def model_torch(net, x, gt, alpha, eps_q, eps_p):
+    """Model's training forward (KLD, dcd) in torch, the reference's four heads; the project's FPS kernel picks y."""
+    import torch
+    import torch.nn.functional as F
+    from torch.distributions import Normal, kl_divergence
+    from ured_hip import group
+    Bn, Z = x.shape[0], net.size_z
+    idx = group.fps(gt, x.shape[2], start=torch.zeros(Bn, dtype=torch.int32, device=gt.device)).long()
+    y = gt.gather(1, idx.unsqueeze(-1).expand(-1, -1, 3)).transpose(1, 2)
+    feat = pcn_encoder_torch(net.encoder, torch.cat((x, y), 0))
+    fx = F.relu(feat[:Bn])
+    o_x = lrb_torch(net.posterior_infer2, lrb_torch(net.posterior_infer1, fx))
+    o_y = lrb_torch(net.prior_infer, feat[Bn:])
+    q = Normal(o_x[:, :Z], F.softplus(o_x[:, Z:]))
+    p = Normal(o_y[:, :Z], F.softplus(o_y[:, Z:]))
+    z = torch.cat((q.loc + q.scale * eps_q, p.loc + p.scale * eps_p), 0)
+    dl_rec = kl_divergence(Normal(torch.zeros_like(p.loc), torch.ones_like(p.scale)), p)
+    dl_g = kl_divergence(Normal(p.loc.detach(), p.scale.detach()), q)
+    code = torch.cat((fx, fx), 0) + lrb_torch(net.generator, z)
+    clouds = [c.transpose(1, 2).contiguous() for c in decoder_torch(net.decoder, code, torch.cat((x, x), 0))]
+    gt2 = torch.cat((gt, gt), 0)
+    ta, nl = net.loss_opts["alpha"], net.loss_opts["lambda"]
+    l = [dcd_torch(c, gt2, ta * 2 if i == 0 else ta, nl) for i, c in enumerate(clouds)]
+    return l[0].mean() * 10 + l[1].mean() * 0.5 + l[2].mean() + l[3].mean() * alpha + (dl_rec.mean() + dl_g.mean()) * 20
 
 
 # ---------------- timing ----------------
@@ -317,6 +378,30 @@ def run_leg(leg, B, iters, rounds):
             res["max_abs_diff"] = float((a[0] - b[0]).abs().max())              # coarse_raw: before any search or selection
             res["coarse_high_max_abs_diff"] = float((a[1] - b[1]).abs().max())  # after the encoder's two kNN versions
         fns = {"hip": lambda: step(lambda: net(gf, pin)), "torch": lambda: step(lambda: decoder_torch(net, gf, pin))}
+    elif i == 6:
+        import types
+        Mo = MODEL
+        args = types.SimpleNamespace(layers="1,1,1,1", knn_list=str(KNN), distribution_loss="KLD", loss="dcd",
+                                     loss_opts={"alpha": Mo["t_alpha"], "lambda": Mo["n_lambda"]}, eval_emd=False,
+                                     num_fps=Mo["num_fps"], num_points=Mo["num_points"], num_coarse=Mo["num_coarse"],
+                                     num_coarse_raw=Mo["num_coarse_raw"], pk=PK, local_folding=True, points_label=True)
+        net = M.Model(args, size_z=Mo["size_z"]).to(dev).eval()
+        x = (torch.rand(B, 3, Mo["n"], generator=g) * 2 - 1).to(dev)
+        gt = (torch.rand(B, Mo["n_gt"], 3, generator=g) * 2 - 1).to(dev)
+        eps = [torch.randn(B, Mo["size_z"], generator=g).to(dev) for _ in range(2)]
+        leaves = [q for q in net.parameters()]
+
+        def step(fwd):
+            for t in leaves:
+                t.grad = None
+            fwd().backward()
+        with torch.no_grad():
+            a, b = net(x, gt, alpha=Mo["alpha"], noise=eps)[2], model_torch(net, x, gt, Mo["alpha"], *eps)
+            res["total_hip"], res["total_torch"] = float(a), float(b)
+            res["max_abs_diff"] = abs(float(a) - float(b))       # of the two totals (the two kNN versions differ in a few rows)
+        res["decoder_clouds"] = 2 * B
+        fns = {"hip": lambda: step(lambda: net(x, gt, alpha=Mo["alpha"], noise=eps)[2]),
+               "torch": lambda: step(lambda: model_torch(net, x, gt, Mo["alpha"], *eps))}
     else:
         net = M.SA_SKN_Res_encoder(CIN, [KNN], PK, 64, [1, 1, 1, 1], PTS).to(dev).eval()
         feats = torch.cat((pts.transpose(1, 2), torch.randn(B, CIN - 3, N, generator=g).to(dev)), 1).requires_grad_(True)
